@@ -4,7 +4,7 @@ step -- `hybrid_proDA.step([source], target)` + `update_ema()` = 2x (forward+bac
 DeepLabV2/ResNet-50 + prototype pseudo-labelling + losses + SGD + teacher EMA -- on synthetic 512x1024 batches of 4
 images per GPU (BASELINE.json configs[2]; configs[3] when launched on N GPUs).
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...      # without a launcher: starts the N ranks itself (fresh child processes), or fails
@@ -17,15 +17,22 @@ exchange is onda_amd/dist.py (two collectives per step, the gradient buckets ove
 Other BASELINE configs: `--config 1` (forward-only evaluation of 8 frames), `--config 2` (supervised fwd+bwd+CE+SGD
 step), `--config 5` (the adaptation step at 1024x2048).
 
-The line carries its own context: `dtype` names the arithmetic the convolutions run in; `config.exact_f32` re-times 3
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step`, `dtype` (the arithmetic the
+convolutions run in), the workload, `config.library` (the hash compiled into libonda_hip.so vs the hash of the sources on
+disk); `vs_baseline`, `roofline` and `cpu_baseline` are null.  `--dump-outputs DIR` writes what the last timed step computed
+(its log, the prototypes, a seeded sample of the student's and the teacher's parameters; per config) to DIR/<name>.npy;
+the inputs are the same in every run.
+
+`--full` adds the side measurements and checks (each `--no-*` option still drops one): `config.exact_f32` re-times 3
 steps with the exact fp32-MFMA kernels; `config.eager_rocm` times the same step on PyTorch-ROCm eager (MIOpen fp32) in
-this process -- live by default when MIOpen's tuned find-db travels with the tree (tools/miopen_db: seconds), with
+this process -- live when MIOpen's tuned find-db travels with the tree (tools/miopen_db: seconds), with
 `--eager` otherwise (MIOpen's kernel search: ~10 minutes), and `vs_baseline` = value / that live eager rate;
+`config.conv_accuracy` is the conv path's error against fp64 on a sample; `config.h2d` the host-fed step;
+`config.multi_gpu_exchange_on_one_gpu` the exchange protocol on one RCCL rank;
 `config.other_configs` holds short driver-timed runs of BASELINE configs 1, 2, 5 and of the static branch; `roofline`
 is measured live with HIP events on the launch stream in extra, instrumented steps after the timed region;
 `cpu_baseline` times the CPU oracle (oracle/step.py, the restatement of the reference pinned by the golden vectors) on
-the host cores at the GPU line's batch size, rank 0, N=1; `config.library` ties the binary to the sources (hash
-compiled into libonda_hip.so vs hash of the sources on disk).
+the host cores at the GPU line's batch size, rank 0, N=1.
 """
 import argparse
 import glob
@@ -65,21 +72,32 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--eager", action="store_true",
-                    help="time the step on PyTorch-ROCm eager in this process even without a tuned MIOpen find-db in the tree "
-                         "(MIOpen's kernel search then takes ~10 minutes)")
+                    help="with --full: time the step on PyTorch-ROCm eager in this process even without a tuned MIOpen find-db "
+                         "in the tree (MIOpen's kernel search then takes ~10 minutes)")
     ap.add_argument("--no-eager", action="store_true")
     ap.add_argument("--eager-only", action="store_true", help=argparse.SUPPRESS)  # the child process of the time-boxed eager leg
     ap.add_argument("--no-exact-f32", action="store_true")
     ap.add_argument("--h2d", action="store_true",
                     help="the batches start in pinned HOST memory and are uploaded every step on a copy stream (the drop-in's "
-                         "real input path); the default line reports this as a second number, config.h2d")
+                         "real input path); a --full line reports this as a second number, config.h2d")
     ap.add_argument("--no-h2d-leg", action="store_true")
     ap.add_argument("--no-exchange-probe", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short runs of BASELINE configs 1, 2, 5 and of the static branch (config.other_configs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks: roofline, exact-fp32 leg, host-fed leg, eager and CPU "
+                         "baselines, other configs, exchange probe, conv accuracy (the --no-* options still drop single ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
     if args.height is None:
         args.height, args.width = (1024, 2048) if args.config == 5 else (512, 1024)
+    if args.eager and not args.full:
+        ap.error("--eager is a leg of the --full line: run `bench.py --full --eager`")
+    if not args.full:
+        # a plain run times the steps and nothing else
+        args.no_cpu_baseline = args.no_roofline = args.no_eager = args.no_exact_f32 = True
+        args.no_h2d_leg = args.no_exchange_probe = args.no_other_configs = True
     return args
 
 
@@ -183,6 +201,61 @@ def timed_loop(fn, warmup, steps, device):
     tmax = torch.tensor([dt], device=device, dtype=torch.float64)
     odist.all_reduce_max(tmax)
     return tmax.item(), out
+
+
+# ------------------------------------------------------------------------------------------------- outputs (--dump-outputs)
+DUMP_SAMPLE = 1 << 20  # elements kept of a larger output: a fixed, seeded sample (4 MB per float32 file)
+DUMP_SEED = 20240
+
+
+def _sample(t):
+    """`t` as float32 numpy: whole when it has at most DUMP_SAMPLE elements, else the same seeded sample of DUMP_SAMPLE
+    positions of it flattened, every run (sorted indices drawn on the CPU, so they do not depend on the device)."""
+    t = t.detach().float()
+    if t.numel() <= DUMP_SAMPLE:
+        return t.cpu().numpy()
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+    return t.reshape(-1)[idx.to(t.device)].cpu().numpy()
+
+
+def _params(model):
+    return _sample(torch.cat([p.detach().reshape(-1) for p in model.parameters()]))
+
+
+def _log_outputs(log):
+    """The step's log dictionary: every numeric entry as `log_<key>` (scalars in float64)."""
+    import re
+
+    import numpy as np
+    out = {}
+    for key, value in log.items():
+        name = "log_" + re.sub(r"[^0-9a-z]+", "_", str(key).lower()).strip("_")
+        if torch.is_tensor(value):
+            out[name] = np.asarray(value.detach().double().item(), np.float64) if value.numel() == 1 else _sample(value)
+        elif isinstance(value, (int, float)) and not isinstance(value, bool):
+            out[name] = np.asarray(value, np.float64)
+    return out
+
+
+def adaptation_outputs(da, log):
+    """What a caller of the adaptation step has after it: the returned log, the prototypes, and the student's and the
+    EMA teacher's parameters (a seeded sample: DeepLabV2 holds ~43 M of them)."""
+    out = _log_outputs(log)
+    out["prototypes"] = _sample(da.prototypes.prototypes)
+    out["student_parameters_sample"] = _params(da.model)
+    out["teacher_parameters_sample"] = _params(da.ema_model)
+    return out
+
+
+def write_outputs(outputs, where):
+    import numpy as np
+    os.makedirs(where, exist_ok=True)
+    total = sum(a.nbytes for a in outputs.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes (more than 64 MB)"
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(where, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------- roofline
@@ -331,7 +404,7 @@ MIOPEN_DB = os.path.join(ROOT, "tools", "miopen_db")  # MIOpen's user find-db + 
 
 
 def miopen_db_ready():
-    """Has MIOpen's kernel search for this workload's convolutions been done before (`python bench.py --eager` on an MI355X
+    """Has MIOpen's kernel search for this workload's convolutions been done before (`python bench.py --full --eager` on an MI355X
     fills tools/miopen_db) and do its results travel with the tree?  Then the live eager leg costs seconds instead of ten minutes."""
     return bool(glob.glob(os.path.join(MIOPEN_DB, "*.ufdb.txt")) or glob.glob(os.path.join(MIOPEN_DB, "*.udb.txt")))
 
@@ -406,7 +479,7 @@ def eager_rocm_boxed(args):
            "--width", str(args.width), "--branch", args.branch]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     # MIOpen appends to its user db and kernel cache whenever it meets something new: the child works on a COPY of the tracked
-    # directory (1.7 MB), so that a measurement run never dirties the tree (`python bench.py --eager` is the run that fills it)
+    # directory (1.7 MB), so that a measurement run never dirties the tree (`python bench.py --full --eager` fills it)
     import shutil
     scratch = tempfile.mkdtemp(prefix="onda_miopen_")
     shutil.copytree(MIOPEN_DB, os.path.join(scratch, "db"))
@@ -514,6 +587,8 @@ def run_adaptation(args, device, rank, world):
         feeder = HostFeeder(src, trg, device) if (args.h2d and shards == 1) else None
         step = lambda i: one_step(da, src, trg, i, total + 8, shards, feeder)  # noqa: E731
         dt, log = timed_loop(step, args.warmup, args.steps, device)
+        # (taken before any leg below steps the model on)
+        outputs = adaptation_outputs(da, log) if (args.dump_outputs and rank == 0) else None
         branch = "dynamic" if da.model_select.current == 1 else "static"
         h2d = None
         if not args.h2d and not args.no_h2d_leg and shards == 1 and rank == 0 and world == 1 and not args.no_roofline:
@@ -561,7 +636,7 @@ def run_adaptation(args, device, rank, world):
         cfg["step_conv_tflops_per_gpu"] = round(tflop_step / (dt / args.steps), 2)
     return {"metric": f"adaptation-step images/sec (fwd+bwd+proto) {args.height}x{args.width} bs={args.batch}",
             "value": round(images * args.steps / dt, 4), "unit": "images/s", "dt": dt,
-            "scaling": "strong" if args.global_batch else "weak", "config": cfg, "roofline": roof}
+            "scaling": "strong" if args.global_batch else "weak", "config": cfg, "roofline": roof, "outputs": outputs}
 
 
 def run_segmentation(args, device, rank, world):
@@ -582,6 +657,10 @@ def run_segmentation(args, device, rank, world):
                for i in range(2)]
     step = lambda i: tr.step(batches[i % 2], 1000)  # noqa: E731
     dt, loss = timed_loop(step, args.warmup, args.steps, device)
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        outputs = _log_outputs({"loss": loss})
+        outputs["parameters_sample"] = _params(model)
     roof = None if args.no_roofline else measure_roofline(step, args.warmup + args.steps, record=(rank == 0))
     gf = CONV_GFLOP.get((args.height, args.width))
     tf = args.batch * (gf[0] + gf[1]) / 1e3 if gf else None
@@ -593,7 +672,7 @@ def run_segmentation(args, device, rank, world):
         cfg_out["step_conv_tflops_per_gpu"] = round(tf / (dt / args.steps), 2)
     return {"metric": f"supervised-step images/sec (fwd+bwd+CE+SGD) {args.height}x{args.width} bs={args.batch}",
             "value": round(world * args.batch * args.steps / dt, 4), "unit": "images/s", "dt": dt, "scaling": "weak",
-            "config": cfg_out, "roofline": roof}
+            "config": cfg_out, "roofline": roof, "outputs": outputs}
 
 
 def run_forward_only(args, device, rank, world):
@@ -622,6 +701,12 @@ def run_forward_only(args, device, rank, world):
         return hist
 
     dt, _ = timed_loop(step, args.warmup, args.steps, device)
+    # the confusion matrix the passes accumulated, and the class scores (`out` head) of the last batch of frames
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        with torch.no_grad():
+            logits = model(fresh(frames[-1])["image"])[1]["out"]
+        outputs = {"confusion_matrix": hist.double().cpu().numpy(), "last_frames_logits": _sample(logits)}
     roof = None if args.no_roofline else measure_roofline(step, 0, record=(rank == 0))
     gf = CONV_GFLOP.get((args.height, args.width))
     cfg_out = {"workload": f"forward-only evaluation of 8 frames {args.width}x{args.height} in batches of {per} (eval-mode forward + "
@@ -629,7 +714,7 @@ def run_forward_only(args, device, rank, world):
                "baseline_config": 1, "global_batch": 8 * world, "parallelism": f"dp{world} (replicas: no exchange)",
                "conv_tflop_per_step_per_gpu": 8 * gf[0] / 1e3 if gf else None}
     return {"metric": f"forward-only frames/sec {args.height}x{args.width}", "value": round(world * 8 * args.steps / dt, 4),
-            "unit": "images/s", "dt": dt, "scaling": "weak", "config": cfg_out, "roofline": roof}
+            "unit": "images/s", "dt": dt, "scaling": "weak", "config": cfg_out, "roofline": roof, "outputs": outputs}
 
 
 def other_configs(args, device):
@@ -649,7 +734,7 @@ def other_configs(args, device):
     for name, over, run in plan:
         sub = copy.copy(args)
         sub.warmup, sub.steps, sub.no_roofline, sub.no_exact_f32, sub.global_batch = 1, 3, True, True, 0
-        sub.h2d, sub.no_h2d_leg = False, True
+        sub.h2d, sub.no_h2d_leg, sub.dump_outputs = False, True, None
         for k, v in over.items():
             setattr(sub, k, v)
         try:
@@ -746,10 +831,13 @@ def main():
     run = {1: run_forward_only, 2: run_segmentation, 3: run_adaptation, 5: run_adaptation}[args.config]
     res = run(args, device, rank, world)
     dt = res.pop("dt")
+    outputs = res.pop("outputs")
+    if outputs is not None:
+        write_outputs(outputs, args.dump_outputs)
     cpu = eager = others = eager_note = None
     headline = args.config in (3, 5) and not args.global_batch
     default_line = headline and args.config == 3 and (args.height, args.width) == (512, 1024) and args.batch == 4
-    if rank == 0 and world == 1 and headline:
+    if rank == 0 and world == 1 and headline and args.full:
         import gc
         gc.collect()
         torch.cuda.empty_cache()
@@ -769,7 +857,9 @@ def main():
             cpu = cpu_baseline(args)
     if rank == 0:
         dtype, note = arithmetic()
-        res["config"].update({"conv_mode": note, "conv_accuracy": conv_accuracy_probe(device), "library": lib})
+        res["config"].update({"conv_mode": note, "library": lib})
+        if args.full:
+            res["config"]["conv_accuracy"] = conv_accuracy_probe(device)
         vs = None
         if others:
             res["config"]["other_configs"] = others
@@ -781,7 +871,7 @@ def main():
             vs = round(res["value"] / eager["images_per_s"], 3)
             res["config"]["vs_baseline_is"] = ("value / config.eager_rocm.images_per_s: the same step on PyTorch-ROCm eager (MIOpen "
                                                "fp32, tuned), timed live in this run on this GPU (BASELINE.md holds no published number)")
-        elif default_line:
+        elif default_line and args.full:
             if eager_note:
                 res["config"]["eager_rocm_skipped"] = eager_note
             # no tuned MIOpen find-db in the tree and no --eager: the committed measurement of the same step (same GPU

@@ -151,8 +151,20 @@ def test_g6_optimizer(golden):
     assert mine1 == g1 and len(g1) == 29
 
 
+@pytest.fixture
+def capture_threads():
+    """The thread count make_golden.py captured with (8).  Through two train-mode steps on random weights the CPU's
+    summation order -- which follows the thread count -- moves the post-step weights by more than the digests' 1e-3: at
+    4 or 32 threads the same oracle on the same CPU misses them.  (A CPU whose convolution kernels block differently
+    still can: the step-1 digests are a property of the capture's kind of host.)"""
+    n = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(n)
+
+
 @pytest.mark.parametrize("tag,head_scale", [("static", 40.0), ("dynamic", 3.0)])
-def test_g7_full_step(golden, tag, head_scale):
+def test_g7_full_step(golden, tag, head_scale, capture_threads):
     g = golden(f"g7_step_{tag}")
     sd = oracle_sd(1, head_scale)
     src = [synth_batch(2, 64, 128, seed=100 + i) for i in range(2)]
