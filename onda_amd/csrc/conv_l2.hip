@@ -2614,11 +2614,16 @@ int onda_conv2d_wgrad_l2(const void* xl, int64_t xplane, const float* xamax, con
                          float* slabs, int lddy, int splitk, const OndaConv* c, onda_stream_t s) {
   ONDA_REQUIRE(xl && dyl && xamax && dyamax && slabs && c && splitk >= 1);
   ONDA_REQUIRE(c->Cin % 8 == 0 && c->Cout % 8 == 0 && c->ldx % 32 == 0 && lddy % 32 == 0);
-  // a caller's pixel table: at least this batch's rows per tap (a larger batch's table of the same geometry is fine)
+  // a caller's pixel table: at least this batch's rows per tap (a larger batch's table of the same geometry is fine), rows
+  // of whole 16-byte groups (the kernel reads four entries at a time), and int32 input-pixel entries that cannot wrap
+  // (the same B*Hi*Wi guard onda_conv2d_wgrad_l2_table_stride applies before it sizes a table)
   ONDA_REQUIRE(c->pix_table == nullptr || c->pix_stride >= ((long long)c->B * c->Ho * c->Wo + 31) / 32 * 32 + 64);
+  ONDA_REQUIRE(c->pix_table == nullptr || c->pix_stride % 4 == 0);
+  ONDA_REQUIRE(c->pix_table == nullptr || (long long)c->B * c->Hi * c->Wi < (1ll << 31));
   (void)xplane;
   (void)dyplane;  // (limb rows: kept in the signature)
   if (!ONDA_ALIGNED16(xl) || !ONDA_ALIGNED16(dyl) || !ONDA_ALIGNED16(slabs)) return ONDA_EALIGN;
+  if (c->pix_table != nullptr && !ONDA_ALIGNED16(c->pix_table)) return ONDA_EALIGN;
   const long long M = (long long)c->B * c->Ho * c->Wo;
   ONDA_REQUIRE(M > 0 && M < (1ll << 31));
   const long long x_total = (long long)c->B * c->Hi * c->Wi * c->ldx * 4;
