@@ -366,6 +366,24 @@ int onda_seg_loss_fwd(const float* logits, int ldl, const int64_t* labels, float
 int onda_seg_loss_bwd(const float* logits, int ldl, const int64_t* labels, const float* result, const float* gscale,
                       float w_ce, float w_rce, float w_reg, float* dlogits, int64_t N, int K, onda_stream_t s);
 
+/* ---- general target loss (prototypes.py:29-39 regular_loss, :299-333; loss.py:48-85 js_divergance) ----
+ * The same CE / RCE plus a selectable regulariser (0: none, 1: MRKLD = -sum log p / (N*K),
+ * 2: MRENT = sum p log p / N, natural log) and the ProDA Jensen-Shannon term
+ * JS = sum_pixels sum_k [-a log2(a+1e-30) + (y log2(y+1e-30) + mp log2(mp+1e-30)) / 2] / (log2(K) * n_mask),
+ * y = one-hot clamped to [1e-4, 1] (all 1e-4 at an ignored pixel), mp = p * (label != 255), a = (y + mp) / 2;
+ * every pixel enters MRKLD / MRENT and the JS numerator, ignored ones included (K * 5e-5 each in JS).
+ * fwd: result (8 floats) = {ce, rce, reg, js, n_valid, n_mask, total, 0}, total = the sum of
+ * w * term over the terms whose weight is non-zero; bwd: dlogits = g * d(total)/dlogits, using
+ * the normalisers left in `result` by fwd, called with the same regulariser and weights;
+ * columns K..ldl-1 of dlogits are zeroed.  ws: 8*(N/256+1).
+ * All labels 255 (n_mask == 0): js = +inf and, with w_js != 0, every element of dlogits is NaN
+ * -- the reference's division by mask.sum() -- while reg stays finite. */
+int onda_target_loss_fwd(const float* logits, int ldl, const int64_t* labels, int regularizer, float w_ce, float w_rce,
+                         float w_reg, float w_js, float* result, float* ws, int64_t N, int K, onda_stream_t s);
+int onda_target_loss_bwd(const float* logits, int ldl, const int64_t* labels, int regularizer, float w_ce, float w_rce,
+                         float w_reg, float w_js, const float* result, const float* gscale, float* dlogits, int64_t N,
+                         int K, onda_stream_t s);
+
 /* ---- prototypes (framework/domain_adaptation/methods/prototype_handler.py) ----------------
  * sigma (:53-60) from the state; then per pixel (:111-166): D[k] = || (f - p_k) / sigma ||
  * (mahalanobis=1) or || f - p_k ||, minus its minimum; P = softmax(-D/tau); P *= prior;

@@ -181,6 +181,185 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restri
   }
 }
 
+// ---- CE + RCE + (MRKLD | MRENT) + JS ------------------------------------------------------------
+// The general target loss of prototypes.py:299-333.  JS follows loss.py:48-85 term by term: y = one-hot clamped to
+// [1e-4, 1] (all 1e-4 at an ignored pixel), mp = p * mask, a = (y + mp) / 2, v * log2(v + 1e-30) per entry; a pixel's
+// numerator is sum_k [-a log2(a+eps) + (y log2(y+eps) + mp log2(mp+eps)) / 2] and JS = sum / (log2(K) * n_mask).
+enum { REG_NONE = 0, REG_MRKLD = 1, REG_MRENT = 2 };
+constexpr float JS_EPS = 1e-30f;
+constexpr float JS_FLOOR = 1e-4f;
+
+__device__ __forceinline__ float xlog2x(float x) { return x * log2f(x + JS_EPS); }
+// d/dx [x log2(x + eps)]
+__device__ __forceinline__ float dxlog2x(float x) { return log2f(x + JS_EPS) + x / ((x + JS_EPS) * 0.69314718056f); }
+
+__global__ __launch_bounds__(256) void target_loss_fwd_kernel(const float* __restrict__ logits, int ldl,
+                                                              const int64_t* __restrict__ labels, int reg_kind,
+                                                              float* __restrict__ ws, int64_t N, int K) {
+  __shared__ float red[6 * 4];
+  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  float part[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // ce, rce, reg, js numerator, n_valid, n_mask
+  if (n < N) {
+    const float* row = logits + (size_t)n * ldl;
+    float v[KMAX];
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < K) {
+        v[k] = row[k];
+        m = fmaxf(m, v[k]);
+      }
+    // p = exp(v - m) / sum and log p = (v - m) - log(sum), as softmax / log_softmax form them: v - (m + log(sum)) would
+    // carry the rounding of m + log(sum) (an ulp of the largest logit) into every p
+    float sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < K) {
+        v[k] -= m;
+        sum += expf(v[k]);
+      }
+    const float lsum = logf(sum);
+    const int64_t tl = labels[n];
+    const bool valid = tl >= 0 && tl != 255 && tl < K;
+    const bool mask = tl != 255;
+    const float fm = mask ? 1.f : 0.f;
+    float ce = 0.f, others = 0.f, reg = 0.f, js = 0.f;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < K) {
+        const float lp = v[k] - lsum;
+        const float p = expf(v[k]) / sum;
+        if (valid && k == (int)tl) ce = -lp;
+        if (mask && k != (int)tl) others += p;
+        if (reg_kind == REG_MRKLD) reg -= lp;
+        if (reg_kind == REG_MRENT) reg += p * lp;
+        const float y = (mask && k == (int)tl) ? 1.f : JS_FLOOR;
+        const float mp = p * fm;
+        const float a = (y + mp) / 2.f;
+        js += -xlog2x(a) + (xlog2x(y) + xlog2x(mp)) / 2.f;
+      }
+    part[0] = ce;
+    part[1] = mask ? -LOG_CLAMP * others : 0.f;
+    part[2] = reg;
+    part[3] = js;
+    part[4] = valid ? 1.f : 0.f;
+    part[5] = fm;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    const float r = wave_sum(part[j]);
+    if (lane == 0) red[j * 4 + wave] = r;
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    const int j = threadIdx.x;
+    ws[(size_t)blockIdx.x * 8 + j] = red[j * 4 + 0] + red[j * 4 + 1] + red[j * 4 + 2] + red[j * 4 + 3];
+  }
+}
+
+// result = {ce, rce, reg, js, n_valid, n_mask, total}; block partials summed in block order in double
+__global__ void target_loss_finalize_kernel(const float* __restrict__ ws, int nblocks, int reg_kind, int64_t N, int K,
+                                            float w_ce, float w_rce, float w_reg, float w_js,
+                                            float* __restrict__ result) {
+  if (threadIdx.x != 0) return;
+  double s[6] = {0, 0, 0, 0, 0, 0};
+  for (int b = 0; b < nblocks; ++b)
+    for (int j = 0; j < 6; ++j) s[j] += (double)ws[(size_t)b * 8 + j];
+  const double ce = s[0] / s[4];  // 0/0 = NaN as in the reference
+  const double rce = s[1] / (s[5] + 1e-6);
+  const double reg = reg_kind == REG_MRKLD ? s[2] / ((double)N * K) : reg_kind == REG_MRENT ? s[2] / (double)N : 0.0;
+  const double js = s[3] / (log2((double)K) * s[5]);  // n_mask == 0: +inf, as the reference's division by mask.sum()
+  // only the terms with a weight enter the total, as the reference adds them under `if weight > 0`
+  double total = 0.0;
+  if (w_ce != 0.f) total += (double)w_ce * ce;
+  if (w_rce != 0.f) total += (double)w_rce * rce;
+  if (w_reg != 0.f) total += (double)w_reg * reg;
+  if (w_js != 0.f) total += (double)w_js * js;
+  result[0] = (float)ce;
+  result[1] = (float)rce;
+  result[2] = (float)reg;
+  result[3] = (float)js;
+  result[4] = (float)s[4];
+  result[5] = (float)s[5];
+  result[6] = (float)total;
+  result[7] = 0.f;
+}
+
+__global__ __launch_bounds__(256) void target_loss_bwd_kernel(const float* __restrict__ logits, int ldl,
+                                                              const int64_t* __restrict__ labels, int reg_kind,
+                                                              const float* __restrict__ result,
+                                                              const float* __restrict__ gscale, float w_ce, float w_rce,
+                                                              float w_reg, float w_js, float* __restrict__ dl, int64_t N,
+                                                              int K) {
+  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const float gs = gscale ? gscale[0] : 1.f;
+  const float nvalid = result[4], nmask = result[5];
+  const float a_ce = nvalid > 0.f ? gs * w_ce / nvalid : 0.f;
+  const float a_rce = gs * w_rce * (-LOG_CLAMP) / (nmask + 1e-6f);
+  const float a_reg = reg_kind == REG_MRKLD   ? gs * w_reg / ((float)N * (float)K)
+                      : reg_kind == REG_MRENT ? gs * w_reg / (float)N
+                                              : 0.f;
+  // n_mask == 0 makes this +inf and the gradient NaN, as in the reference; without JS nothing of it is used
+  const bool use_js = w_js != 0.f;
+  const float a_js = use_js ? gs * w_js / (log2f((float)K) * nmask) : 0.f;
+  const float* row = logits + (size_t)n * ldl;
+  float v[KMAX];
+  float m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k)
+    if (k < K) {
+      v[k] = row[k];
+      m = fmaxf(m, v[k]);
+    }
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k)
+    if (k < K) {
+      v[k] -= m;
+      sum += expf(v[k]);
+    }
+  const float lsum = logf(sum);
+  const int64_t tl = labels[n];
+  const bool valid = tl >= 0 && tl != 255 && tl < K;
+  const bool mask = tl != 255;
+  const float fm = mask ? 1.f : 0.f;
+  // r[k] = d(a_reg*MRENT + a_js*JS)/dp_k of this pixel; its softmax Jacobian is p_k (r_k - sum_j p_j r_j)
+  float r[KMAX];
+  float pt = 0.f, pr = 0.f;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k)
+    if (k < K) {
+      const float lp = v[k] - lsum;
+      v[k] = expf(v[k]) / sum;  // p, as the forward pass has it
+      if (k == (int)tl) pt = v[k];
+      float rk = reg_kind == REG_MRENT ? a_reg * lp : 0.f;
+      if (use_js) {
+        const float y = (mask && k == (int)tl) ? 1.f : JS_FLOOR;
+        const float mp = v[k] * fm;
+        const float a = (y + mp) / 2.f;
+        rk += a_js * (0.5f * (dxlog2x(mp) - dxlog2x(a))) * fm;
+      }
+      r[k] = rk;
+      pr += v[k] * rk;
+    }
+  float* out = dl + (size_t)n * ldl;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) {
+    if (k >= ldl) break;
+    float g = 0.f;
+    if (k < K) {
+      const float onehot = (k == (int)tl) ? 1.f : 0.f;
+      if (valid) g += a_ce * (v[k] - onehot);
+      if (mask) g += a_rce * pt * (v[k] - onehot);
+      if (reg_kind == REG_MRKLD) g += a_reg * ((float)K * v[k] - 1.f);
+      g += v[k] * (r[k] - pr);
+    }
+    out[k] = g;
+  }
+}
+
 // ---- prototypes ---------------------------------------------------------------------------
 __global__ void proto_sigma_kernel(const float* __restrict__ proto, const float* __restrict__ sqmean,
                                    const float* __restrict__ counter, float* __restrict__ sigma, int K, int C) {
@@ -676,6 +855,29 @@ int onda_seg_loss_bwd(const float* logits, int ldl, const int64_t* labels, const
   const int nb = (int)((N + 255) / 256);
   hipLaunchKernelGGL(seg_loss_bwd_kernel, dim3(nb), dim3(256), 0, ONDA_STREAM(s), logits, ldl, labels, result, gscale,
                      w_ce, w_rce, w_reg, dlogits, N, K);
+  return ONDA_LAUNCH_RESULT();
+}
+
+int onda_target_loss_fwd(const float* logits, int ldl, const int64_t* labels, int regularizer, float w_ce, float w_rce,
+                         float w_reg, float w_js, float* result, float* ws, int64_t N, int K, onda_stream_t s) {
+  ONDA_REQUIRE(logits && labels && result && ws && K >= 1 && K <= KMAX && ldl >= K && N >= 1 && regularizer >= REG_NONE &&
+               regularizer <= REG_MRENT);
+  const int nb = (int)((N + 255) / 256);
+  hipLaunchKernelGGL(target_loss_fwd_kernel, dim3(nb), dim3(256), 0, ONDA_STREAM(s), logits, ldl, labels, regularizer, ws,
+                     N, K);
+  hipLaunchKernelGGL(target_loss_finalize_kernel, dim3(1), dim3(64), 0, ONDA_STREAM(s), ws, nb, regularizer, N, K, w_ce,
+                     w_rce, w_reg, w_js, result);
+  return ONDA_LAUNCH_RESULT();
+}
+
+int onda_target_loss_bwd(const float* logits, int ldl, const int64_t* labels, int regularizer, float w_ce, float w_rce,
+                         float w_reg, float w_js, const float* result, const float* gscale, float* dlogits, int64_t N,
+                         int K, onda_stream_t s) {
+  ONDA_REQUIRE(logits && labels && result && dlogits && K >= 1 && K <= KMAX && ldl >= K && ldl <= KMAX && N >= 1 &&
+               regularizer >= REG_NONE && regularizer <= REG_MRENT);
+  const int nb = (int)((N + 255) / 256);
+  hipLaunchKernelGGL(target_loss_bwd_kernel, dim3(nb), dim3(256), 0, ONDA_STREAM(s), logits, ldl, labels, regularizer,
+                     result, gscale, w_ce, w_rce, w_reg, w_js, dlogits, N, K);
   return ONDA_LAUNCH_RESULT();
 }
 

@@ -71,13 +71,14 @@ def _flat_int_buffers(module):
 
 
 def regular_loss(regularizer, activation):
-    """"MRKLD": -mean(log_softmax(activation)) over every element (reference :35-38)."""
+    """"MRKLD": -mean(log_softmax(activation)) over every element (reference :35-38); "MRENT": sum(p * log p) over every
+    element / (B*h*w) (:32-34); any other name: 0."""
+    if regularizer not in ("MRKLD", "MRENT"):
+        return 0
+    labels = torch.zeros(activation.shape[0], *activation.shape[2:], dtype=torch.int64, device=activation.device)
     if regularizer == "MRKLD":
-        return ops.seg_losses(activation, torch.zeros(activation.shape[0], *activation.shape[2:], dtype=torch.int64,
-                                                      device=activation.device), 0.0, 0.0, 1.0)[0]
-    if regularizer == "MRENT":
-        raise NotImplementedError("onda_amd: the MRENT regulariser is not used by the BASELINE configs")
-    return 0
+        return ops.seg_losses(activation, labels, 0.0, 0.0, 1.0)[0]
+    return ops.target_losses(activation, labels, 0.0, 0.0, 1.0, "MRENT", 0.0)[0]
 
 
 def _positive(v):
@@ -385,11 +386,17 @@ class online_proDA(da_model):
         batch_size, channels, w, h = out.size()
         predictions = proto_pred["pseudolabels"].reshape(batch_size, w, h)
         w_ce, w_rce, w_reg = _positive(spec.RCE_ALPHA), _positive(spec.RCE_BETA), _positive(spec.REGULARIZER_WEIGHT)
-        if w_reg > 0 and spec.REGULARIZER != "MRKLD":
-            raise NotImplementedError("onda_amd: only the MRKLD regulariser is implemented")
-        if spec.JS_D > 0:
-            raise NotImplementedError("onda_amd: JS_D is 0 in every shipped config")
-        total, ce_loss, rce_loss, reg_loss = ops.seg_losses(out, predictions, w_ce, w_rce, w_reg)
+        w_js = _positive(spec.JS_D)
+        js_loss = 0
+        if w_js > 0 or (w_reg > 0 and spec.REGULARIZER != "MRKLD"):
+            # MRENT / an unknown regulariser (0, as the reference's regular_loss) and the JS term (reference :323-333);
+            # the shipped configs (MRKLD, JS_D 0) keep the CE + RCE + MRKLD kernel below
+            total, ce_loss, rce_loss, reg_loss, js_loss = ops.target_losses(out, predictions, w_ce, w_rce, w_reg,
+                                                                            spec.REGULARIZER, w_js)
+            if spec.REGULARIZER not in ops.REGULARIZERS:
+                reg_loss = 0
+        else:
+            total, ce_loss, rce_loss, reg_loss = ops.seg_losses(out, predictions, w_ce, w_rce, w_reg)
         flat = proto_pred["pseudolabels"].reshape(-1)
         return {
             "ce_loss": ce_loss if w_ce > 0 else 0,
@@ -398,7 +405,7 @@ class online_proDA(da_model):
             "rce_loss": rce_loss if w_rce > 0 else 0,
             "sym_loss": total,  # the reference aliases total_loss = sym_loss
             "regularization_loss": reg_loss if w_reg > 0 else 0,
-            "JS Divergance loss": 0,
+            "JS Divergance loss": js_loss if w_js > 0 else 0,
             "Total target loss": total,
             "model regularization": 0,
         }

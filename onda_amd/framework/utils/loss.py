@@ -1,5 +1,5 @@
 """Drop-in for the hot-path functions of ``framework/utils/loss.py``: ``cross_entropy_2d``
-(:16-45) and ``rce`` (:88-112), hard-label branches, on the fused HIP loss kernel."""
+(:16-45), ``rce`` (:88-112) and ``js_divergance`` (:62-85), hard-label branches, on the fused HIP loss kernels."""
 from onda_amd import ops
 
 
@@ -21,3 +21,10 @@ def rce(pred, labels, device, soft=False):
     if soft:
         raise NotImplementedError("onda_amd: soft-label RCE (SOFT_LABELS) is not on the hybrid_switch hot path")
     return ops.seg_losses(pred, labels, 0.0, 1.0, 0.0)[0]
+
+
+def js_divergance(pred, labels, device):
+    """ProDA's Jensen-Shannon term (reference :62-85) on the fused HIP target-loss kernel: the one-hot of `labels` clamped
+    to [1e-4, 1] against softmax(pred) masked to the kept pixels, divided by the kept-pixel count (+inf, with a NaN
+    gradient, when every label is 255 -- as the reference)."""
+    return ops.target_losses(pred, labels, 0.0, 0.0, 0.0, "none", 1.0)[0]

@@ -1,5 +1,5 @@
-"""The segmentation head's tail: class slices, fused CE / RCE / MRKLD, softmax statistics, bilinear upsampling (+ fused
-cross-entropy / argmax / confusion matrix), the device-side prior select."""
+"""The segmentation head's tail: class slices, fused CE / RCE / MRKLD (and, off the default path, MRENT and the JS term),
+softmax statistics, bilinear upsampling (+ fused cross-entropy / argmax / confusion matrix), the device-side prior select."""
 import ctypes
 import os
 from ctypes import byref
@@ -76,6 +76,50 @@ class SegLossFn(torch.autograd.Function):
 
 def seg_losses(out, labels, w_ce=1.0, w_rce=0.0, w_reg=0.0):
     return SegLossFn.apply(out, labels, float(w_ce), float(w_rce), float(w_reg))
+
+
+REGULARIZERS = {"MRKLD": 1, "MRENT": 2}  # any other name contributes 0, as in the reference's regular_loss
+
+
+class TargetLossFn(torch.autograd.Function):
+    """w_ce*CE + w_rce*RCE + w_reg*reg + w_js*JS over hard labels, one pass; reg is MRKLD, MRENT or nothing (selector
+    0 / 1 / 2, REGULARIZERS) and JS the ProDA Jensen-Shannon term.  Returns (total, ce, rce, reg, js) with gradients
+    flowing through `total` only; a term whose weight is 0 is left out of `total`.  Every label 255: js = +inf and, with
+    w_js > 0, a NaN gradient, as in the reference."""
+
+    @staticmethod
+    def forward(ctx, out, labels, w_ce, w_rce, w_reg, regularizer, w_js):
+        rows, ld, N, K = logits_rows(out)
+        labels = labels.reshape(-1).to(device=out.device, dtype=torch.int64).contiguous()
+        result = torch.empty(8, device=out.device, dtype=torch.float32)
+        ws = torch.empty(8 * (N // 256 + 1), device=out.device, dtype=torch.float32)
+        call("onda_target_loss_fwd", _p(rows), ld, _p(labels), regularizer, w_ce, w_rce, w_reg, w_js, _p(result), _p(ws),
+             N, K, _stream())
+        ctx.save_for_backward(rows, labels, result)
+        ctx.meta = (ld, N, K, w_ce, w_rce, w_reg, regularizer, w_js, tuple(out.shape))
+        ce, rce, reg, js, total = result[0], result[1], result[2], result[3], result[6].clone()
+        ctx.mark_non_differentiable(ce, rce, reg, js)
+        ctx.set_materialize_grads(False)
+        return total, ce, rce, reg, js
+
+    @staticmethod
+    def backward(ctx, gtotal, _a, _b, _c, _d):
+        if gtotal is None:
+            return None, None, None, None, None, None, None
+        rows, labels, result = ctx.saved_tensors
+        ld, N, K, w_ce, w_rce, w_reg, regularizer, w_js, shape = ctx.meta
+        B, _, H, W = shape
+        dl = torch.empty(B, H, W, ld, device=rows.device, dtype=torch.float32)
+        g = gtotal.reshape(1).to(torch.float32).contiguous()
+        call("onda_target_loss_bwd", _p(rows), ld, _p(labels), regularizer, w_ce, w_rce, w_reg, w_js, _p(result), _p(g),
+             _p(dl), N, K, _stream())
+        return dl[..., :K].permute(0, 3, 1, 2), None, None, None, None, None, None
+
+
+def target_losses(out, labels, w_ce=1.0, w_rce=0.0, w_reg=0.0, regularizer="MRKLD", w_js=0.0):
+    """The reference's whole hard-label target loss (prototypes.py:299-333): (total, ce, rce, reg, js)."""
+    return TargetLossFn.apply(out, labels, float(w_ce), float(w_rce), float(w_reg), REGULARIZERS.get(regularizer, 0),
+                              float(w_js))
 
 
 def softmax_stats(out, want_probs=False, want_argmax=False):
