@@ -331,7 +331,10 @@ int onda_upsample_bwd(const float* dout_nchw, float* dlogits, int ldl, int B, in
 /* fused supervised-loss head: loss_calc(interp(logits), label) (segmentation.py:70-80 -> func.py:35-42 -> loss.py:16-45) without
  * the upsampled tensor.  labels u8[B,H,W] (values >= K, i.e. 255, are ignored); result[0] = mean CE over the kept pixels (NaN
  * when none is kept, as the reference), result[1] = their number; ws: onda_upsample_ce_ws floats.  bwd: dlogits[B,h,w] rows of
- * stride ldl (columns >= K zeroed) = gscale[0] (or 1) * w_ce * d result[0] / d logits: two separable gather passes, deterministic. */
+ * stride ldl (columns >= K zeroed) = gscale[0] (or 1) * w_ce * d result[0] / d logits: two separable gather passes, deterministic.
+ * onda_upsample_ce_fused: 1 when the backward takes the width pair w -> W (its row pass needs one low-resolution column's output
+ * span in LDS: upsampling factors up to ~211x), 0 otherwise -- the caller then upsamples and takes the loss unfused. */
+int onda_upsample_ce_fused(int w, int W);
 int64_t onda_upsample_ce_ws(int B, int H, int W);
 int onda_upsample_ce_fwd(const float* logits, int ldl, const uint8_t* labels, float* result, float* ws, int B, int h, int w, int K,
                          int H, int W, onda_stream_t s);

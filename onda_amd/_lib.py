@@ -106,6 +106,7 @@ SIGNATURES = {
     "onda_upsample_fwd": (I, [P, I, P, I, I, I, I, I, I, P]),
     "onda_upsample_bwd": (I, [P, P, I, I, I, I, I, I, I, P]),
     "onda_upsample_argmax": (I, [P, I, P, I, I, I, I, I, I, P]),
+    "onda_upsample_ce_fused": (I, [I, I]),
     "onda_upsample_ce_ws": (L, [I, I, I]),
     "onda_upsample_ce_fwd": (I, [P, I, P, P, P, I, I, I, I, I, I, P]),
     "onda_upsample_ce_bwd_ws": (L, [I, I, I, I]),

@@ -530,6 +530,13 @@ static inline unsigned ew_grid(size_t total) {
 // align_corners scale exactly as ATen computes it (float division, 0 when out size is 1)
 static inline float ac_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 
+// low-resolution columns per pass-A workgroup of the fused head's backward: as many as keep its output span within UCE_SPAN
+// pixels; below 1 (upsampling factors past ~211x along x) the fused head does not take the shape
+static inline int uce_block_cols(int w, int W) {
+  int CW = (int)((UCE_SPAN - 6) * ac_scale(w, W)) - 2;
+  return CW > 64 ? 64 : CW;
+}
+
 }  // namespace
 
 extern "C" {
@@ -622,6 +629,8 @@ int onda_upsample_argmax_hist(const float* logits, int ldl, const uint8_t* label
   return ONDA_LAUNCH_RESULT();
 }
 
+int onda_upsample_ce_fused(int w, int W) { return w > 1 && W > 1 && uce_block_cols(w, W) >= 1; }
+
 int64_t onda_upsample_ce_ws(int B, int H, int W) { return 2 * (int64_t)ew_grid((size_t)B * H * W); }
 
 int onda_upsample_ce_fwd(const float* logits, int ldl, const uint8_t* labels, float* result, float* ws, int B, int h, int w, int K,
@@ -640,9 +649,7 @@ int onda_upsample_ce_bwd(const float* logits, int ldl, const uint8_t* labels, co
                          float* dlogits, float* ws, int B, int h, int w, int K, int H, int W, onda_stream_t s) {
   ONDA_REQUIRE(logits && labels && result && dlogits && ws && K <= ldl && K <= UCE_KMAX && h > 1 && w > 1 && H > 1 && W > 1);
   const float sy = ac_scale(h, H), sx = ac_scale(w, W);
-  // low-resolution columns per pass-A workgroup: as many as keep its output span within UCE_SPAN pixels
-  int CW = (int)((UCE_SPAN - 6) * sx) - 2;
-  if (CW > 64) CW = 64;
+  const int CW = uce_block_cols(w, W);
   ONDA_REQUIRE(CW >= 1);
   const size_t lds = ((size_t)(CW + 2) * K + (size_t)UCE_SPAN * K + 2 * UCE_SPAN) * sizeof(float);
   // 19 classes: 59 KB.  Every K the forward accepts (<= UCE_KMAX = 32: 95 KB) has to run backward as well (round-4 advisor): above

@@ -188,8 +188,22 @@ class UpsampleCEFn(torch.autograd.Function):
         return dl[..., :K].permute(0, 3, 1, 2), None
 
 
+_UCE_FUSED = {}  # (w, W) -> does the fused head's backward take the width pair
+
+
 def upsample_ce(out, labels):
-    return UpsampleCEFn.apply(out, labels)
+    """loss_calc(interp(out), label).  Fused (UpsampleCEFn) wherever its backward runs; past ~211x upsampling along x, where
+    one low-resolution column's output span no longer fits the backward's row pass, UpsampleFn followed by torch's
+    cross-entropy under the same label contract (values >= K ignored; no kept pixel: NaN, gradient zeros)."""
+    key = (out.shape[3], labels.shape[2])
+    if key not in _UCE_FUSED:
+        _UCE_FUSED[key] = bool(query("onda_upsample_ce_fused", *key))
+    if _UCE_FUSED[key]:
+        return UpsampleCEFn.apply(out, labels)
+    K = out.shape[1]
+    labels = labels.to(device=out.device, dtype=torch.uint8).long()
+    up = UpsampleFn.apply(out, tuple(labels.shape[1:]))
+    return torch.nn.functional.cross_entropy(up, labels.masked_fill(labels >= K, -100), ignore_index=-100)
 
 
 def upsample_argmax(out, size):
