@@ -353,6 +353,20 @@ int onda_upsample_argmax(const float* logits, int ldl, uint8_t* cls, int B, int 
 int onda_upsample_argmax_hist(const float* logits, int ldl, const uint8_t* labels, int64_t* hist, uint8_t* cls, int B,
                               int h, int w, int K, int H, int W, onda_stream_t s);
 
+/* ---- expected calibration error (monitoring.py:99-136 ECE.record on adaptation_model.py:145-149 / prototypes.py:191-200) ----
+ * rows: [B*h*w] rows of ld floats, K <= 255 classes in front; 1 <= bins <= 2^20.  Every output pixel of the align_corners bilinear upsample to HxW is
+ * reduced to (confidence, class): probs = 0 interpolates, then takes the softmax over K; probs = 1 interpolates only (rows hold
+ * probabilities).  table: int64[bins + 1][3], accumulated (zero it first), 16-byte aligned:
+ *   [r][0] += round(conf * 2^32)   [r][1] += (class == label)   [r][2] += 1        (every pixel, whatever its label)
+ * r = floor(conf / gap) on float32 with gap = (float)(1.0 / bins) -- ATen's floor division -- clamped to [0, bins - 1] (the
+ * reference raises at conf >= 1 + gap); a non-finite conf counts (0, 0, 1) into row `bins`.  |conf| is taken down to 2^30
+ * before the conversion.  Integer adds: the table does not depend on the order or the grid.
+ * hist (optional, int64[K*K]): the confusion matrix exactly as onda_upsample_argmax_hist counts it, in the same pass.
+ * onda_ece_bins_local: up to this many bins a workgroup counts in LDS and flushes once; above it, global atomics per pixel. */
+int onda_ece_bins_local(void);
+int onda_upsample_ece(const float* rows, int ld, const uint8_t* labels, int64_t* table, int bins, int probs, int64_t* hist, int B,
+                      int h, int w, int K, int H, int W, onda_stream_t s);
+
 /* ---- per-pixel softmax statistics --------------------------------------------------------
  * probs (optional, rows of stride ldp) = softmax(logits row); argmax (optional int32);
  * result[0] = mean over pixels of the max probability (the "prior ..." / "model" monitor

@@ -299,6 +299,164 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
   }
 }
 
+// ---- expected calibration error: upsample -> (softmax) -> (confidence, class) -> bin table, one pass ------------------------
+// ECE.record(interp(pred).softmax(1), label) (monitoring.py:99-136, adaptation_model.py:145-149) without the upsampled tensor:
+// one thread per output pixel interpolates its K values in registers (same weights, same expression, same first-maximum rule
+// as upsample_kernel), reduces them to a confidence and a class, and counts into table[bins + 1][3] (int64):
+//   [row][0] += round(conf * 2^32)   [row][1] += (class == label)   [row][2] += 1
+// row = floor(conf / gap) for the float32 conf and gap (what ATen's fmod-based floor division yields), clamped to
+// [0, bins - 1]; a non-finite conf counts (0, 0, 1) into row `bins`.  Every pixel is counted, whatever its label.
+// Fixed point: integer adds give the same table for any order and grid.  conf * 2^32 is exact for conf >= 2^-9 (a float has
+// 24 bits; the maximum of K <= 255 probabilities is >= 1/255) and rounds to nearest below; |conf| is taken down to 2^30
+// first (probs mode accepts any number), so the conversion itself cannot overflow.
+constexpr float ECE_FIX = 4294967296.f;      // 2^32: an int64 sum holds 2^31 pixels at conf = 1 (Cityscapes val at 1024x2048: 1.05e9)
+constexpr float ECE_CONF_CAP = 1073741824.f; // 2^30
+constexpr int ECE_BINS_LDS = 2047;           // bins a workgroup counts in LDS ((bins + 1) * 16 bytes <= 32 KB); more: global atomics
+constexpr int ECE_KREG = 32;                 // classes kept in registers between the maximum and the exponentials; more: recomputed
+
+__device__ __forceinline__ int ece_row(float conf, float gap, int bins) {
+  if (!(fabsf(conf) <= 3.402823466e38f)) return bins;  // NaN, +-inf
+  // correctly rounded division (no fast-math in this build), and bins <= 2^20 (host check), so q < 2^20 is within 2^-4 of the
+  // quotient: its floor is off by one at the most
+  const float q = conf / gap;
+  if (!(q < (float)bins)) return bins - 1;
+  if (q < 0.f) return 0;
+  int n = (int)q;
+  // the sign of conf - n * gap from one rounding of the exact value (monotonic; 0 and gap are floats)
+  const float r = fmaf(-(float)n, gap, conf);
+  if (r < 0.f) --n;
+  else if (r >= gap) ++n;
+  return n < 0 ? 0 : (n >= bins ? bins - 1 : n);
+}
+
+// LDS: sum[rows] (u64), then per row (correct << 32 | pixels) (u64): a workgroup sees fewer than 2^32 pixels (host check).
+template <bool KREG>
+__global__ __launch_bounds__(256) void upsample_ece_kernel(const float* __restrict__ rows, int ldl,
+                                                           const uint8_t* __restrict__ gt, unsigned long long* __restrict__ table,
+                                                           int bins, float gap, int probs, unsigned long long* __restrict__ hist,
+                                                           int B, int h, int w, int K, int H, int W, float sy, float sx, int local) {
+  extern __shared__ unsigned long long ece_lds[];
+  __shared__ unsigned lh[UPS_HIST_LDS];
+  const int R = bins + 1, KK = K * K;
+  unsigned long long* lsum = ece_lds;
+  unsigned long long* lcnt = ece_lds + R;
+  const bool hlocal = hist != nullptr && KK <= UPS_HIST_LDS;
+  if (local)
+    for (int i = threadIdx.x; i < 2 * R; i += blockDim.x) ece_lds[i] = 0ull;
+  if (hlocal)
+    for (int i = threadIdx.x; i < KK; i += blockDim.x) lh[i] = 0u;
+  __syncthreads();
+  const bool vec = (ldl & 3) == 0 && ((K + 3) & ~3) <= ldl && (reinterpret_cast<uintptr_t>(rows) & 15) == 0;
+  const size_t total = (size_t)B * H * W;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    int arg = 0;
+    const int X = (int)(e % W);
+    const size_t q = e / W;
+    const int Y = (int)(q % H), b = (int)(q / H);
+    const Lerp ly = lerp_index(Y, sy, h), lx = lerp_index(X, sx, w);
+    const float* p00 = rows + (((size_t)b * h + ly.i0) * w + lx.i0) * ldl;
+    const float* p01 = rows + (((size_t)b * h + ly.i0) * w + lx.i1) * ldl;
+    const float* p10 = rows + (((size_t)b * h + ly.i1) * w + lx.i0) * ldl;
+    const float* p11 = rows + (((size_t)b * h + ly.i1) * w + lx.i1) * ldl;
+    // the four classes k .. k + 3 (those >= K: 0, never looked at)
+    auto group = [&](int k, float* o) {
+      f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = a, d = a, f = a;
+      if (vec) {
+        a = LD4(p00 + k), c = LD4(p01 + k), d = LD4(p10 + k), f = LD4(p11 + k);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (k + j < K) a[j] = p00[k + j], c[j] = p01[k + j], d[j] = p10[k + j], f[j] = p11[k + j];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = ly.l0 * (lx.l0 * a[j] + lx.l1 * c[j]) + ly.l1 * (lx.l0 * d[j] + lx.l1 * f[j]);  // = upsample_kernel
+    };
+    float best = -INFINITY, v[KREG ? ECE_KREG : 4];
+    bool bad = false;
+    if (KREG) {
+#pragma unroll
+      for (int k = 0; k < ECE_KREG; k += 4)
+        if (k < K) {
+          group(k, v + k);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (k + j < K) {
+              bad |= v[k + j] != v[k + j];
+              if (v[k + j] > best) best = v[k + j], arg = k + j;
+            }
+        }
+    } else {
+      for (int k = 0; k < K; k += 4) {
+        group(k, v);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (k + j < K) {
+            bad |= v[j] != v[j];
+            if (v[j] > best) best = v[j], arg = k + j;
+          }
+      }
+    }
+    float conf = bad ? NAN : best;  // (torch.max: a NaN among the K values is the maximum)
+    if (!probs) {
+      float sum = 0.f;
+      if (KREG) {
+#pragma unroll
+        for (int k = 0; k < ECE_KREG; ++k)
+          if (k < K) sum += expf(v[k] - best);
+      } else {
+        for (int k = 0; k < K; k += 4) {
+          group(k, v);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (k + j < K) sum += expf(v[j] - best);
+        }
+      }
+      conf = 1.f / sum;  // softmax of the maximum: exp(0) / sum; NaN when a value is NaN or +inf
+    }
+    const int g = gt[e], row = ece_row(conf, gap, bins);
+    long long fix = 0;
+    if (row < bins) fix = __float2ll_rn(fminf(fmaxf(conf, -ECE_CONF_CAP), ECE_CONF_CAP) * ECE_FIX);
+    const unsigned long long hit = row < bins && arg == g ? 1ull : 0ull;
+    if (local) {
+      if (fix) atomicAdd(&lsum[row], (unsigned long long)fix);
+      atomicAdd(&lcnt[row], (hit << 32) | 1ull);
+    } else {
+      if (fix) atomicAdd(&table[(size_t)row * 3], (unsigned long long)fix);
+      if (hit) atomicAdd(&table[(size_t)row * 3 + 1], 1ull);
+      atomicAdd(&table[(size_t)row * 3 + 2], 1ull);
+    }
+    if (hist && g < K) {  // = upsample_kernel
+      if (hlocal) atomicAdd(&lh[g * K + arg], 1u);
+      else atomicAdd(&hist[g * K + arg], 1ull);
+    }
+  }
+  __syncthreads();
+  if (local) {
+    // every workgroup starts its flush at a different row, as the confusion matrix below
+    const int start = (int)((blockIdx.x * 37u) % (unsigned)R);
+    for (int i = threadIdx.x; i < R; i += blockDim.x) {
+      int r = i + start;
+      if (r >= R) r -= R;
+      const unsigned long long c = lcnt[r];
+      if (c) {
+        const unsigned long long s = lsum[r];
+        if (s) atomicAdd(&table[(size_t)r * 3], s);
+        if (c >> 32) atomicAdd(&table[(size_t)r * 3 + 1], c >> 32);
+        atomicAdd(&table[(size_t)r * 3 + 2], c & 0xffffffffull);
+      }
+    }
+  }
+  if (hlocal) {
+    const int start = (int)((blockIdx.x * 37u) % (unsigned)KK);
+    for (int i = threadIdx.x; i < KK; i += blockDim.x) {
+      int cell = i + start;
+      if (cell >= KK) cell -= KK;
+      const unsigned n = lh[cell];
+      if (n) atomicAdd(&hist[cell], (unsigned long long)n);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restrict__ dout, float* __restrict__ dl,
                                                            int ldl, int B, int h, int w, int K, int H, int W, float sy,
                                                            float sx, float inv_sy, float inv_sx) {
@@ -626,6 +784,33 @@ int onda_upsample_argmax_hist(const float* logits, int ldl, const uint8_t* label
   hipLaunchKernelGGL((upsample_kernel<true>), dim3(grid), dim3(256), 0, ONDA_STREAM(s), logits,
                      ldl, (float*)nullptr, cls, labels, reinterpret_cast<unsigned long long*>(hist), B, h, w, K, H, W,
                      ac_scale(h, H), ac_scale(w, W));
+  return ONDA_LAUNCH_RESULT();
+}
+
+int onda_ece_bins_local(void) { return ECE_BINS_LDS; }
+
+int onda_upsample_ece(const float* rows, int ld, const uint8_t* labels, int64_t* table, int bins, int probs, int64_t* hist, int B,
+                      int h, int w, int K, int H, int W, onda_stream_t s) {
+  ONDA_REQUIRE(rows && labels && table && K >= 1 && K <= ld && K <= 255 && bins >= 1 && bins <= (1 << 20) && B >= 1 && h >= 1 &&
+               w >= 1 && H >= 1 && W >= 1);
+  if (!ONDA_ALIGNED16(table) || (hist && !ONDA_ALIGNED16(hist))) return ONDA_EALIGN;
+  const size_t total = (size_t)B * H * W;
+  const int local = bins <= ECE_BINS_LDS;
+  unsigned grid = ew_grid(total);
+  // one flush of the workgroup's rows each: two workgroups per CU of long-lived counters instead of one per 256 pixels
+  if ((local || (hist && K * K <= UPS_HIST_LDS)) && grid > 512u) grid = 512u;
+  ONDA_REQUIRE(total / grid < (1ull << 32) - 256);  // (correct << 32 | pixels) per workgroup
+  const size_t lds = local ? (size_t)(bins + 1) * 16 : 0;
+  const float gap = (float)(1.0 / bins);  // the reference's 1.0 / bins, rounded to float32 where it meets the confidences
+  auto* t = reinterpret_cast<unsigned long long*>(table);
+  auto* hh = reinterpret_cast<unsigned long long*>(hist);
+  const float sy = ac_scale(h, H), sx = ac_scale(w, W);
+  if (K <= ECE_KREG)
+    hipLaunchKernelGGL((upsample_ece_kernel<true>), dim3(grid), dim3(256), lds, ONDA_STREAM(s), rows, ld, labels, t, bins, gap,
+                       probs ? 1 : 0, hh, B, h, w, K, H, W, sy, sx, local);
+  else
+    hipLaunchKernelGGL((upsample_ece_kernel<false>), dim3(grid), dim3(256), lds, ONDA_STREAM(s), rows, ld, labels, t, bins, gap,
+                       probs ? 1 : 0, hh, B, h, w, K, H, W, sy, sx, local);
   return ONDA_LAUNCH_RESULT();
 }
 

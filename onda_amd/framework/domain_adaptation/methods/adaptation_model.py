@@ -4,6 +4,8 @@ optimizer construction, LR schedule, evaluation, checkpoints) and ``evaluation``
 
 Evaluation computes the class map with the fused upsample->argmax kernel (no 159 MB
 upsampled tensor); the confusion matrix stays the reference's numpy bincount.
+With ``OTHERS.ECE_SKIP`` off, the expected calibration error comes out of the same pass
+(upsample -> softmax -> max -> bin table, ``ops.upsample_ece``).
 """
 import abc
 import os
@@ -18,6 +20,7 @@ from onda_amd import ops
 from onda_amd.config import unset
 from onda_amd.optim import ReplaySGD
 from onda_amd.framework.utils.func import lr_poly, per_class_iu
+from onda_amd.framework.utils.monitoring import ECE
 
 
 def switch_batch_statistics(model, setting, batchnorms=None):
@@ -76,10 +79,7 @@ class da_model:
         self.model, self.cfg, self.cfg_spec = model, cfg, cfg_spec
         self.device = cfg.OTHERS.DEVICE
         self.bn = batchnorm_stats(model)
-        if not (isinstance(cfg.OTHERS.ECE_SKIP, bool) and cfg.OTHERS.ECE_SKIP):
-            raise NotImplementedError("onda_amd: ECE recording is outside the hot path; set OTHERS.ECE_SKIP: True "
-                                      "(as hybrid_switch.yml / static_model.yml do)")
-        self.ece_record = False
+        self.ece_record = not (isinstance(cfg.OTHERS.ECE_SKIP, bool) and cfg.OTHERS.ECE_SKIP)
         # the reference's torch.optim.SGD(model.optim_parameters(lr), ...) (:88-93): same parameter groups, duplicates
         # included; ReplaySGD replays the for-loop semantics of those duplicates in one HIP launch
         self.optimizer = ReplaySGD(model.optim_parameters(cfg_spec.LEARNING_RATE), lr=cfg_spec.LEARNING_RATE,
@@ -108,8 +108,14 @@ class da_model:
         for group, ratio in zip(self.optimizer.param_groups, self.cfg.MODEL.LR_RATIO.split(":")):
             group["lr"] = base * int(ratio)
 
+    def ece_bins(self):
+        """OTHERS.BINS, 1000 when unset (reference :134)."""
+        return 1000 if unset(self.cfg.OTHERS.BINS) else self.cfg.OTHERS.BINS
+
     def evaluate(self, validation_loader, additional_func={}):
-        """mIoU of the student (and of any extra prediction function) over a loader."""
+        """mIoU of the student (and of any extra prediction function) over a loader; with OTHERS.ECE_SKIP off also the
+        expected calibration error of each (reference :134-165: ECE of interp(pred).softmax(1), into eval_metric_list as
+        "ece <predictor>"), counted by the same launch as the confusion matrix."""
         function_dict = {"model": lambda x: self.model(x["image"].to(self.device))[1]["out"]}
         function_dict.update(additional_func)
         self.models_eval()
@@ -117,11 +123,17 @@ class da_model:
         # the confusion matrices live on the GPU; one read-back per evaluation instead of a class
         # map per image (the fused kernel upsamples, takes the argmax and bins against the labels)
         counters = {key: torch.zeros(n, n, dtype=torch.int64, device=self.device) for key in function_dict}
+        ece_recorder = {key: ECE(self.ece_bins()) for key in function_dict} if self.ece_record else {}
         with torch.no_grad():
             for batch in validation_loader:
                 for key, func in function_dict.items():
-                    ops.upsample_argmax_hist(func(batch), batch["label"], counters[key], n)
+                    if self.ece_record:
+                        ece_recorder[key].record_lowres(func(batch), batch["label"], self.interp.size, probs=False,
+                                                        hist=counters[key], num_classes=n)
+                    else:
+                        ops.upsample_argmax_hist(func(batch), batch["label"], counters[key], n)
         self.models_default_config()
+        self.eval_metric_list.extend(("ece " + name, ece().item()) for name, ece in ece_recorder.items())
         return {key: per_class_iu(count.cpu().numpy()) for key, count in counters.items()}
 
     def evaluate_all(self, validation_loaders):

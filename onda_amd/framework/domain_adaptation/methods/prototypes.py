@@ -32,7 +32,7 @@ from onda_amd.config import unset
 from onda_amd.framework.domain_adaptation.methods.adaptation_model import da_model, switch_batch_statistics
 from onda_amd.framework.domain_adaptation.methods.prototype_handler import prototype_handler
 from onda_amd.framework.model import deeplabv2
-from onda_amd.framework.utils.monitoring import Monitor
+from onda_amd.framework.utils.monitoring import ECE, Monitor
 from onda_amd.synthetic import feature_hw as synthetic_feature_hw
 
 
@@ -189,6 +189,7 @@ class online_proDA(da_model):
         if not unset(spec.MODEL_REGULARIZATION) and spec.MODEL_REGULARIZATION > 0:
             raise NotImplementedError("onda_amd: EWC model regularisation is disabled in every shipped config")
         self.model_regularization = None
+        self.ece_save = {}
         if isinstance(spec.BN_POLICY, dict):
             self.cfg_spec.BN_POLICY = "freeze"
         if not unset(spec.LOAD_MODEL) and spec.LOAD_MODEL:
@@ -265,6 +266,24 @@ class online_proDA(da_model):
         total, ce, rc, _ = ops.seg_losses(out, label.long().to(self.device), w_ce, w_rce, 0.0)
         return {"buff_ce_loss": ce if w_ce > 0 else 0, "buff_rce_loss": rc if w_rce > 0 else 0, "buff_loss": total}
 
+    # ---- calibration of the priors (evaluation only) -------------------------------------------------------------------
+    def record_ece(self, name, prediction, label, shape=None):
+        """ECE of interp(prediction) against `label` under "ece <name>" (reference :191-200): recorded only while the
+        monitor is frozen, i.e. under ``evaluate``.  `prediction`: low-resolution probabilities, NCHW or an [N,K] map
+        with shape=(B, h, w); they are upsampled inside the kernel and no softmax follows."""
+        if not self.ece_record or not self.intensity_ma.freeze:
+            return
+        name = "ece " + name
+        if name not in self.ece_save:
+            self.ece_save[name] = ECE(self.ece_bins())
+        self.ece_save[name].record_lowres(prediction if shape is None else (prediction, shape), label, self.interp.size,
+                                          probs=True)
+
+    def register_ece(self):
+        if self.ece_record:
+            self.eval_metric_list.extend((name, ece().item()) for name, ece in self.ece_save.items())
+            self.ece_save = {}
+
     # ---- pieces of the target side ---------------------------------------------------------------------------------
     def _device_image(self, batch):
         img = batch["image"]
@@ -274,23 +293,28 @@ class online_proDA(da_model):
         self._img_cache = (img, dev)
         return dev
 
-    def _forward_prior(self, model, image, want_argmax=False, mask=None):
-        """One no-grad forward: (output dict, softmax map [N,K], mean max-probability (device scalar), argmax or None)."""
+    def _forward_prior(self, model, image, want_argmax=False, mask=None, ece=None):
+        """One no-grad forward: (output dict, softmax map [N,K], mean max-probability (device scalar), argmax or None).
+        `ece` = (name, labels): the prior's record point of an evaluation (reference :216, :226, :241)."""
         if mask is not None:
             deeplabv2.force_mask(mask)
         pred = model(image)[1]
         conf, probs, am = ops.softmax_stats(pred["out"], want_probs=True, want_argmax=want_argmax)
+        if ece is not None and ece[1] is not None:
+            b, _, h, w = pred["out"].shape
+            self.record_ece(ece[0], probs, ece[1], shape=(b, h, w))
         return pred, probs, conf, am
 
-    def _teacher_static(self, image, teacher_mask=None):
+    def _teacher_static(self, image, teacher_mask=None, ece_label=None):
         """Teacher pass (train mode) and, with STATIC_LAMBDA > 0, the static model's pass; their confidences are NOT
-        read here."""
-        t = {}
-        t["pred"], prior_ema, t["conf_ema"], t["cls"] = self._forward_prior(self.ema_model, image, True, teacher_mask)
+        read here.  `ece_label`: the labels of an evaluation batch (prototype_predictions only; the step passes none)."""
+        t = {"ece_label": ece_label}
+        t["pred"], prior_ema, t["conf_ema"], t["cls"] = self._forward_prior(self.ema_model, image, True, teacher_mask,
+                                                                            ece=("ema", ece_label))
         t["prior"] = self.cfg_spec.EMA_LAMBDA * prior_ema
         t["conf_static"] = None
         if self.cfg_spec.STATIC_LAMBDA > 0:
-            _, prior_static, t["conf_static"], _ = self._forward_prior(self.static_model, image)
+            _, prior_static, t["conf_static"], _ = self._forward_prior(self.static_model, image, ece=("static", ece_label))
             t["prior"] += self.cfg_spec.STATIC_LAMBDA * prior_static
         return t
 
@@ -336,7 +360,7 @@ class online_proDA(da_model):
         keep, w_dyn = self._prior_plan()
         prior = t["prior"]
         if w_dyn > 0:
-            _, prior_dynamic, conf_dyn, _ = self._forward_prior(self.dynamic_model, image)
+            _, prior_dynamic, conf_dyn, _ = self._forward_prior(self.dynamic_model, image, ece=("dynamic", t.get("ece_label")))
             deferred.put("prior dynamic", conf_dyn)
             if keep == 0:
                 prior = w_dyn * prior_dynamic
@@ -370,11 +394,16 @@ class online_proDA(da_model):
         """Teacher / static / dynamic priors and prototype pseudo-labels (reference :208-273), everything at once."""
         with torch.no_grad():
             image = self._device_image(batch)
-            t = self._teacher_static(image)
+            # (hybrid_proDA puts a 0 where a batch has no labels: nothing to record against)
+            recording = self.ece_record and self.intensity_ma.freeze and torch.is_tensor(batch.get("label"))
+            t = self._teacher_static(image, ece_label=batch["label"] if recording else None)
             if not self.intensity_ma.freeze:
                 self._record_switch_scalars(t, self._switch_scalars([t]))
             deferred = _Scalars()
             out = self._labels(t, self._mixed_prior(t, image, deferred), deferred)
+            if recording:
+                b, _, h, w = t["pred"]["out"].shape
+                self.record_ece("pure prototypes", out["soft_predictions"], batch["label"], shape=(b, h, w))
             packed = deferred.packed()
             if packed is not None and not self.intensity_ma.freeze:
                 self.intensity_ma.add_device(deferred.keys, odist.all_reduce_mean(packed))
@@ -595,8 +624,11 @@ class online_proDA(da_model):
             return proto_pred["soft_predictions"].reshape(b, h, w, k).permute(0, 3, 1, 2)
 
         if isinstance(self.cfg_spec.SKIP_PROTO_EVAL, bool) and self.cfg_spec.SKIP_PROTO_EVAL:
-            return super().evaluate(validation_loader)
-        return super().evaluate(validation_loader, {"proto": proto_func})
+            evaluation = super().evaluate(validation_loader)
+        else:
+            evaluation = super().evaluate(validation_loader, {"proto": proto_func})
+        self.register_ece()
+        return evaluation
 
     def evaluate_update_dynamic(self):
         if unset(self.cfg_spec.AUTO_DYNAMIC) or not self.cfg_spec.AUTO_DYNAMIC:

@@ -143,6 +143,10 @@ class hybrid_proDA(online_proDA):
         else:
             return t["prior"]
         deferred.put("prior dynamic", ops.gate_scalar(flag, conf_dyn))
+        label = t.get("ece_label")
+        if label is not None and int(flag.item()):  # an evaluation that records ECE (reference :83): only a pass that ran
+            b, _, h, w = t["pred"]["out"].shape
+            self.record_ece("dynamic", prior_dynamic, label, shape=(b, h, w))
         return ops.select_prior(flag, t["prior"], 1.0, prior_dynamic, lam)
 
     def _prior_plan(self):

@@ -1,5 +1,5 @@
 """Drop-in for the hot-path part of ``framework/utils/monitoring.py``: ``Monitor`` (:7-96), the windowed statistics
-behind the static / dynamic switch.
+behind the static / dynamic switch, and ``ECE`` (:99-136), the calibration table of an evaluation.
 
 Same call surface and values as the reference (fixture G5): ``add({key: value})``, ``avg`` = median of the last
 ``limit`` samples, ``exp`` = exponential moving average started at the first sample, ``dev_avg`` = weighted level of
@@ -170,6 +170,81 @@ class Monitor(object):
     def exp_dict(self):
         self._flush()
         return {key: s.ema for key, s in self._series.items()}
+
+
+class ECE:
+    """Expected calibration error over `bins` confidence bins (reference monitoring.py:99-136): same constructor,
+    ``record(prediction, label, axis)`` and ``__call__``; counted differently.
+
+    The table is int64 ``[bins + 1, 3]`` on the device of the first record: per bin the sum of round(conf * 2^32), the
+    number of correct pixels and the number of pixels -- integer adds, so the result does not depend on the order of
+    the pixels or the launches (2^31 pixels at conf = 1 fit).  Bin = ``conf // gap`` on float32 (ATen's floor division,
+    the reference's ``conf_to_bin``), with the two cases in which the reference raises given a meaning: a finite
+    confidence whose bin is >= bins (conf = 1.0 with bins = 4) goes to bin ``bins - 1`` (one below 0 to bin 0), a
+    non-finite one counts (0, 0, 1) into the extra row ``bins`` and makes ``ECE()`` NaN.  Every pixel is counted: a
+    label of 255 is never correct but is in the total, as in the reference.
+
+    ``record`` is the generic torch path for full-resolution tensors; ``record_lowres`` the fused HIP path
+    (ops.upsample_ece: upsample -> softmax -> max -> table without the upsampled tensor)."""
+    FIX = 4294967296.0  # 2^32
+    CAP = 1073741824.0  # |conf| is taken down to 2^30 before the conversion
+
+    def __init__(self, bins) -> None:
+        self.bins = bins
+        self.gap = 1.0 / bins
+        self.table = None
+
+    def _table(self, device):
+        if self.table is None:
+            self.table = torch.zeros(self.bins + 1, 3, dtype=torch.int64, device=device)
+        elif self.table.device != torch.device(device):
+            self.table = self.table.to(device)
+        return self.table
+
+    def conf_to_bin(self, prediction_confidence):
+        """Row of the table for float32 confidences (finite ones; see the class docstring for the rest)."""
+        return torch.floor_divide(prediction_confidence, self.gap).clamp(0, self.bins - 1).long()
+
+    def record(self, prediction, label, axis):
+        conf, cls = prediction.max(axis=axis)
+        conf, cls = conf.reshape(-1).float(), cls.reshape(-1)
+        label = label.reshape(-1).to(conf.device)
+        table = self._table(conf.device)
+        finite = torch.isfinite(conf)
+        safe = torch.where(finite, conf, torch.zeros_like(conf))
+        row = torch.where(finite, self.conf_to_bin(safe), torch.full_like(cls, self.bins))
+        fix = torch.where(finite, torch.round(safe.double().clamp(-self.CAP, self.CAP) * self.FIX).long(), torch.zeros_like(cls))
+        hit = ((cls == label) & finite).long()
+        table.index_add_(0, row, torch.stack([fix, hit, torch.ones_like(hit)], 1))
+
+    def record_lowres(self, rows_or_out, label, size, probs, hist=None, num_classes=None):
+        """``record(interp(x).softmax(1), label, 1)`` (probs=False) or ``record(interp(x), label, 1)`` (probs=True) for
+        low-resolution ``x`` -- NCHW, or an [N,K] map of a [B,h,w] grid given as (map, (B, h, w)) -- and interp =
+        bilinear align_corners to `size` = (H, W), which the labels must have; one HIP launch, which with `hist` also
+        counts the confusion matrix of ops.upsample_argmax_hist."""
+        from onda_amd import ops
+        shape = None
+        if isinstance(rows_or_out, (tuple, list)):
+            rows_or_out, shape = rows_or_out
+        if tuple(label.shape[1:]) != tuple(size):
+            raise RuntimeError(f"onda_amd: labels of {tuple(label.shape[1:])} for an upsample to {tuple(size)}")
+        ops.upsample_ece(rows_or_out, label, self._table(rows_or_out.device), self.bins, probs=probs, hist=hist,
+                         num_classes=num_classes, shape=shape)
+
+    @property
+    def calc_matrix(self):
+        """The reference's float32 [bins, 3] view (summed confidence, correct, pixels) of the table."""
+        t = torch.zeros(self.bins + 1, 3, dtype=torch.int64) if self.table is None else self.table.cpu()
+        m = t[: self.bins].double()
+        m[:, 0] /= self.FIX
+        return m.float()
+
+    def __call__(self):
+        t = torch.zeros(self.bins + 1, 3, dtype=torch.int64) if self.table is None else self.table.cpu()
+        if int(t[self.bins, 2]) > 0:
+            return torch.tensor(float("nan"), dtype=torch.float32)
+        m = t[: self.bins].double()
+        return ((m[:, 0] / self.FIX - m[:, 1]).abs().sum() / m[:, 2].sum()).float()
 
 
 class DeviceSwitch:

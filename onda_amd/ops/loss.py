@@ -227,6 +227,40 @@ def upsample_argmax_hist(out, labels, hist, num_classes):
     return hist
 
 
+def upsample_ece(out_or_rows, labels, table, bins, probs=False, hist=None, num_classes=None, shape=None):
+    """Calibration table of ECE.record(interp(out).softmax(1), label) (probs=False) or ECE.record(interp(out), label)
+    (probs=True: `out` holds probabilities) without the upsampled tensor: table i64[bins + 1, 3] (accumulated) += per bin
+    (sum of round(conf * 2^32), correct, pixels), non-finite confidences in row `bins` (include/onda_hip.h).
+    `out_or_rows`: NCHW logits as upsample_argmax_hist takes them, or an [N,K] map with shape=(B, h, w).  With `hist`
+    (i64[K,K], accumulated) the same launch also counts the confusion matrix of upsample_argmax_hist."""
+    if out_or_rows.dim() == 2:
+        if shape is None:
+            raise ValueError("upsample_ece: an [N,K] map needs shape=(B, h, w)")
+        B, h, w = shape
+        N, K = out_or_rows.shape
+        if N != B * h * w:
+            raise ValueError(f"upsample_ece: {N} rows for shape {tuple(shape)}")
+        out_or_rows = out_or_rows.reshape(B, h, w, K).permute(0, 3, 1, 2)
+    rows, ld, _, K = logits_rows(out_or_rows)
+    if rows.dtype != torch.float32:
+        raise TypeError("upsample_ece: float32 only")
+    B, _, h, w = out_or_rows.shape
+    if num_classes is not None and num_classes != K:
+        raise ValueError(f"upsample_ece: {K} classes in the map, num_classes = {num_classes}")
+    labels = labels.to(device=rows.device, dtype=torch.uint8).contiguous()
+    if labels.dim() != 3 or labels.shape[0] != B:
+        raise ValueError(f"upsample_ece: labels of shape {tuple(labels.shape)} for a batch of {B}")
+    H, W = labels.shape[1:]
+    if table.dtype != torch.int64 or tuple(table.shape) != (bins + 1, 3) or not table.is_contiguous() or table.device != rows.device:
+        raise ValueError(f"upsample_ece: table must be contiguous int64 [{bins + 1}, 3] on {rows.device}")
+    if hist is not None and (hist.dtype != torch.int64 or hist.numel() != K * K or not hist.is_contiguous()
+                             or hist.device != rows.device):
+        raise ValueError(f"upsample_ece: hist must be contiguous int64 [{K}, {K}] on {rows.device}")
+    call("onda_upsample_ece", _p(rows), ld, _p(labels), _p(table), int(bins), int(bool(probs)), _p(hist), B, h, w, K, H, W,
+         _stream())
+    return table
+
+
 # ------------------------------------------------------------------------------- device-side switch
 def select_prior(flag, a, wa, b, wb):
     """flag ? wb * b : wa * a, elementwise, as a true select (`b` may be garbage when flag == 0)."""
