@@ -163,7 +163,7 @@ int onda_conv_l2_variant(int64_t M, int Cout);  /* base tile shape of an (M, Cou
 /* device kernel launched for a problem: 0 / 1 / 2 = conv_l2_kernel<4,2> / <2,2> / <4,1>, 3 = conv_l2x_kernel<4,2> (256x128 tiles,
  * at most 32 K-steps per tile: the continuous K-step stream); bench.py names its per-kernel figures after this.  Short K loops
  * (1x1 convolutions) of a 256x128 problem run as 128x128 tiles on two workgroups per CU where that measured faster (few K-steps,
- * or many column tiles: csrc/conv_l2.hip, l2_variant_k) */
+ * or many column tiles: csrc/conv_l2.hip, l2_plan) */
 int onda_conv_l2_kernel_id(int64_t M, int Cout, int taps, int Cin);
 int onda_conv_l2_tiles_m(int64_t M, int Cout, int taps, int Cin);  /* rows of the `stats` partials the conv writes for this problem */
 /* the same for a launch with a row-group boundary (OndaConv.stat_split) and / or OndaConv.plain_schedule; *tile_rows (optional)

@@ -2224,93 +2224,96 @@ int onda_stem_im2col_l2(const float* x_nchw, const float* xamax, void* dst, int6
   return ONDA_LAUNCH_RESULT();
 }
 
+}  // extern "C"
+
+namespace {
+// The environment switches of the planning, read in ONE place, once per plan.  ONDA_L2_VARIANT: that tile variant for every
+// problem (and neither the short-K rule nor the stationary kernel); ONDA_L2_SHORTK128 (default on): the short-K 128 x 128 rule;
+// ONDA_L2_STATIONARY (default off): the activation-stationary 1 x 1 kernel; ONDA_CONV_SCHED: 1 tile-per-workgroup, 2 hybrid.
+// All but ONDA_L2_SHORTK128, a measurement switch, are read per call: the tests flip them between launches.
+struct L2Overrides { bool has_variant; int variant; bool short_k128, stationary; int sched; };
+L2Overrides l2_overrides() {
+  static const int short_k128 = getenv("ONDA_L2_SHORTK128") ? atoi(getenv("ONDA_L2_SHORTK128")) : 1;
+  const char* v = getenv("ONDA_L2_VARIANT");
+  const char* a = getenv("ONDA_L2_STATIONARY");
+  return {v != nullptr, v ? atoi(v) : 0, short_k128 != 0, a != nullptr && atoi(a) != 0, conv_sched_override()};
+}
+
 // tile variant of the pre-split conv for an (M, Cout) problem: 0 = 256 x 128 (8 waves), 1 = 128 x 128, 2 = 256 x 64
-int onda_conv_l2_variant(int64_t M, int Cout) {
-  if (const char* e = getenv("ONDA_L2_VARIANT")) return atoi(e);
+int l2_variant_mc(long long M, int Cout, const L2Overrides& o) {
+  if (o.has_variant) return o.variant;
   if (Cout <= 64) return 2;
   const long long t256 = ((M + 255) / 256) * ((Cout + 127) / 128);
   return t256 >= 200 ? 0 : 1;
 }
 
-// ... and for an (M, Cout, K) problem: short K loops whose epilogue outweighs them run faster as 128 x 128 tiles on TWO
-// four-wave workgroups per CU (one's epilogue beside the other's K loop) than in the 256 x 128 stream kernel -- when there
-// are many column tiles to share the activation rows in L2, or so few K-steps that the tile is all epilogue.  Measured per
-// shape (tools/ab_conv_shapes.sh with ONDA_L2_VARIANT=1, profiles/r05_short_k_tiles_ab.txt): -4...-23 % where the rule
-// says yes at 4 images, +2...+15 % for 256 output channels with 16-32 K-steps, where it says no; at 8 images the data
-// gradients gain the same and the train-mode forwards are +-3 %; the step: 92.81 -> 92.35 ms (three alternating runs).
-static int l2_variant_k(long long M, int Cout, int taps, int Cin) {
-  const int v = onda_conv_l2_variant(M, Cout);
-  static const int on = getenv("ONDA_L2_SHORTK128") ? atoi(getenv("ONDA_L2_SHORTK128")) : 1;
-  if (v != 0 || !on || getenv("ONDA_L2_VARIANT")) return v;
-  const int kts = taps * (Cin / 32);
-  return kts <= 8 || (kts <= 16 && Cout >= 512) || (kts <= 32 && Cout >= 2048) ? 1 : 0;
-}
+// K-steps per tile up to which a 256 x 128 problem runs as the continuous K-step stream (conv_l2x_kernel): short K loops
+// (1 x 1 convolutions up to 1024 input channels) gain 6-17 % from it; long ones lose ~4 % against the slot-staggered kernel,
+// whose per-tile start / end they amortise anyway (measured per shape, one process).  (Round 6 re-measured the threshold:
+// 72-step tiles -- 256 -> 256 3 x 3 -- 130 us on the stream kernel against 120.5, 144-step tiles 391 against 363.)
+constexpr int L2X_MAX_KSTEPS = 32;
 
-// ... and 1 x 1 convolutions with 64 / 128 / 256 input channels and at least 128 output channels run ACTIVATION-STATIONARY
-// (conv_l2a_kernel: a workgroup's 128 rows in registers, the weight rows streamed): the same 128-row statistic tiles as
-// variant 1, no stream-K remainder.  ONDA_L2_STATIONARY=1 switches it on (default: the tile kernels of round 5).
-static bool l2_stationary(long long M, int Cout, int taps, int Cin) {
-  // OFF by default: measured alone the kernel is 7-18 % faster than the 128 x 128 tile kernel on the train-mode forward convolutions
-  // it takes (256 -> 1024: 76-77 us against 82.7; 128 -> 512: 33.5 against 39.4; 64 -> 256 at 129 x 257: 52 against 64), the
-  // adaptation step does not move (94.88 / 94.87 ms on, 94.77 / 94.72 off, alternating runs on one box): profiles/r06_l2a_*.txt
-  const char* e = getenv("ONDA_L2_STATIONARY");  // (read per call: the kernel's own test switches it on for its launches)
-  if (e == nullptr || atoi(e) == 0 || getenv("ONDA_L2_VARIANT")) return false;
-  // (at least two column tiles: with one, nothing amortises a panel's rows)
-  return taps == 1 && (Cin == 64 || Cin == 128 || Cin == 256) && Cout >= 256 && l2_variant_k(M, Cout, taps, Cin) == 1;
-}
+struct L2Epilogue { bool plain; bool dense_out; long long y_total; };  // what l2_fwd_impl knows and the queries do not
 
-/* which device kernel onda_conv2d_fwd_l2 launches for a problem: the tile variant (0: 256 x 128, 1: 128 x 128, 2: 256 x 64
- * = conv_l2_kernel<4,2> / <2,2> / <4,1>), 3: conv_l2x_kernel<4,2>, the continuous K-step stream taken by 256 x 128
- * problems with at most 32 K-steps per tile, or 4: conv_l2a_kernel, the activation-stationary 1 x 1 kernel (bench.py names
- * its per-kernel figures after this) */
-// K-steps per tile up to which a 256 x 128 problem runs as the continuous K-step stream (conv_l2x_kernel).  (Round 6 re-measured
-// the threshold: 72-step tiles -- 256 -> 256 3 x 3 -- 130 us on the stream kernel against 120.5, 144-step tiles 391 against 363.)
-static constexpr int l2x_max_ksteps() { return 32; }
-
-int onda_conv_l2_kernel_id(int64_t M, int Cout, int taps, int Cin) {
-  if (l2_stationary(M, Cout, taps, Cin)) return 4;
-  const int variant = l2_variant_k(M, Cout, taps, Cin);
-  const bool short_k = taps * (Cin / 32) <= l2x_max_ksteps();
-  return variant == 0 && short_k ? 3 : variant;
-}
-
-}  // extern "C"
-
-namespace {
-// How an (M, Cout, K) problem is scheduled: whole rounds of one tile per workgroup; a remainder of tiles (tiles mod the
-// resident workgroups) is cut into equal K ranges over all workgroups when that pays (hybrid stream-K).
-struct L2Schedule {
-  int variant, BM, BN, tilesM, tilesN, G, rem, sub;
-  bool balanced, stationary;
+/* How onda_conv2d_fwd_l2 / _limbs run an (M, Cout, K) problem, decided HERE and nowhere else: l2_fwd_impl launches what the
+ * plan says, the public queries read it.  kernel: the tile variant (0: 256 x 128, 1: 128 x 128, 2: 256 x 64 = conv_l2_kernel<4,2> /
+ * <2,2> / <4,1>), 3: conv_l2x_kernel<4,2>, the continuous K-step stream, or 4: conv_l2a_kernel, the activation-stationary 1 x 1
+ * kernel (bench.py names its per-kernel figures after this).  grid: workgroups of that kernel.  Whole rounds of one tile per
+ * workgroup; the remainder -- rem = tiles mod the G resident workgroups -- is cut into equal K ranges over all of them when
+ * that pays (balanced: hybrid stream-K, conv_l2_fixup_kernel follows, `sub` statistic rows per remainder tile row). */
+struct L2Plan {
+  int kernel, variant, BM, BN, tilesM, tilesN, grid, G, rem, sub, tiles_dp;
+  bool balanced;
   int rem_rows() const { return tilesM - (tilesM * tilesN - rem) / tilesN; }  // tile rows that hold remainder tiles
   int stats_rows_total() const { return tilesM + (balanced ? rem_rows() * (sub - 1) : 0); }
 };
-bool l2_small_ring2() { return true; }  // (the four-wave tiles on a three-stage ring, one workgroup per CU, lost: DESIGN.md section 3)
 
-L2Schedule l2_schedule(long long M, int Cout, int taps, int Cin, bool have_ws, long long stat_split = 0, bool plain = false) {
-  L2Schedule q;
-  q.variant = l2_variant_k(M, Cout, taps, Cin);
+// `epi` == nullptr: plain epilogue, dense output below 2 GiB -- what the public queries assume.  The queries therefore name
+// a kernel the launch does not take in two cases, left as they are because bench.py's per-kernel figures are keyed by them:
+// with ONDA_L2_STATIONARY on, a launch with a loaded epilogue or a scattered output runs on the 128 x 128 tile kernel (same
+// statistic rows, no remainder) where the query says 4; and a scattered output of 2 GiB or more runs on the 256 x 128 tile
+// kernel where the query says 3 (and onda_conv_l2_live_fraction 1.0, though that kernel skips dead taps).
+L2Plan l2_plan(long long M, int Cout, int taps, int Cin, bool have_ws, long long stat_split, bool plain_schedule, const L2Epilogue* epi) {
+  const L2Overrides o = l2_overrides();
+  const int KT = taps * (Cin / 32);
+  L2Plan q;
+  // Short K loops whose epilogue outweighs them run faster as 128 x 128 tiles on TWO four-wave workgroups per CU (one's
+  // epilogue beside the other's K loop) than in the 256 x 128 stream kernel -- when there are many column tiles to share the
+  // activation rows in L2, or so few K-steps that the tile is all epilogue.  Measured per shape (tools/ab_conv_shapes.sh with
+  // ONDA_L2_VARIANT=1, profiles/r05_short_k_tiles_ab.txt): -4...-23 % where the rule says yes at 4 images, +2...+15 % for 256
+  // output channels with 16-32 K-steps, where it says no; at 8 images the data gradients gain the same and the train-mode
+  // forwards are +-3 %; the step: 92.81 -> 92.35 ms (three alternating runs).
+  q.variant = l2_variant_mc(M, Cout, o);
+  if (q.variant == 0 && o.short_k128 && !o.has_variant && (KT <= 8 || (KT <= 16 && Cout >= 512) || (KT <= 32 && Cout >= 2048)))
+    q.variant = 1;
   q.BM = q.variant == 1 ? 128 : 256;
   q.BN = q.variant == 2 ? 64 : 128;
   q.tilesM = (int)((M + q.BM - 1) / q.BM);
   q.tilesN = (Cout + q.BN - 1) / q.BN;
   // 256 x 128 tiles: one workgroup per CU (144 KB of LDS, 3-stage ring).  The four-wave tiles (128 x 128, 256 x 64) run a
   // 2-stage ring (64 / 80 KB): two workgroups per CU, each covering the other's DMA waits, prologue and epilogue
-  q.G = q.variant == 0 || !l2_small_ring2() ? conv_resident_workgroups() / 2 : conv_resident_workgroups();
+  // (the four-wave tiles on a three-stage ring, one workgroup per CU, lost: DESIGN.md section 3)
+  const int cus = conv_resident_workgroups() / 2;
+  q.G = q.variant == 0 ? cus : 2 * cus;
   q.sub = q.BM / (256 / (q.BN / 4));
-  const int tiles = q.tilesM * q.tilesN, KT = taps * (Cin / 32);
+  const int tiles = q.tilesM * q.tilesN;
   q.rem = tiles % q.G;
   const double t_tile_us = 2.0 * q.BM * q.BN * taps * Cin / 1.4e6;  // one tile on one CU at ~360 TF/s chip-wide
   const double fix_us = 6.0 + (q.G + 2.0 * q.rem) * (q.BM * q.BN / 16384.0) * 0.02;  // partial tiles written + read
   q.balanced = have_ws && q.rem != 0 && KT >= 4 && t_tile_us * (1.0 - (double)q.rem / q.G) > fix_us &&
                (size_t)q.G * 2 * q.BM * q.BN <= (size_t)onda_conv_ws_floats() && q.G <= 1024;
-  if (plain) q.balanced = false;  // OndaConv.plain_schedule
-  q.stationary = l2_stationary(M, Cout, taps, Cin);
-  if (q.stationary) q.balanced = false;  // contiguous runs of (row panel, column tile) items: balanced to one item by construction
-  if (const int force = conv_sched_override()) {  // ONDA_CONV_SCHED: 1 tile-per-workgroup, 2 hybrid
-    if (force == 1 || !have_ws) q.balanced = false;
-    else if (force == 2) q.balanced = q.rem != 0;
-  }
+  if (plain_schedule) q.balanced = false;  // OndaConv.plain_schedule
+  // 1 x 1 convolutions with 64 / 128 / 256 input channels and at least two column tiles (with one, nothing amortises a
+  // panel's rows) run ACTIVATION-STATIONARY where the 128 x 128 tiles would (conv_l2a_kernel: a workgroup's 128 rows in
+  // registers, the weight rows streamed): the same 128-row statistic tiles, no stream-K remainder.  OFF by default: measured
+  // alone the kernel is 7-18 % faster than the tile kernel on the train-mode forward convolutions it takes (256 -> 1024:
+  // 76-77 us against 82.7; 128 -> 512: 33.5 against 39.4; 64 -> 256 at 129 x 257: 52 against 64), the adaptation step does
+  // not move (94.88 / 94.87 ms on, 94.77 / 94.72 off, alternating runs on one box): profiles/r06_l2a_*.txt
+  const bool stationary = o.stationary && !o.has_variant && taps == 1 && (Cin == 64 || Cin == 128 || Cin == 256) && Cout >= 256 &&
+                          q.variant == 1;
+  if (stationary) q.balanced = false;  // contiguous runs of (row panel, column tile) items: balanced to one item by construction
+  if (o.sched == 1 || (o.sched != 0 && !have_ws)) q.balanced = false;  // ONDA_CONV_SCHED: 1 tile-per-workgroup, 2 hybrid
+  else if (o.sched == 2) q.balanced = q.rem != 0;
   // Two row groups with separate BatchNorm statistics (OndaConv.stat_split): the statistics row of the tile that straddles
   // the boundary is split by onda_bn_finalize_l2, which needs that row to cover the WHOLE tile -- a stream-K remainder tile
   // spreads its statistics over sub-block rows.  Remainder tiles are the last ones; keep the straddler out of their tile rows
@@ -2318,16 +2321,31 @@ L2Schedule l2_schedule(long long M, int Cout, int taps, int Cin, bool have_ws, l
   // (the same when the boundary falls BETWEEN two tile rows: the remainder's extra statistic rows sit behind all regular
   //  rows, where the BatchNorm kernels count them with group 1 -- every remainder tile must lie in group 1)
   if (q.balanced && stat_split > 0 && (stat_split + q.BM - 1) / q.BM > (tiles - q.rem) / q.tilesN) q.balanced = false;
+  // conv_l2a_kernel takes the plain epilogue (with or without statistics) and a dense output.  Everything else -- scale /
+  // shift / residual / ReLU / max|y|, limb-row outputs, scattered outputs -- stays on the 128 x 128 tile kernel.  The stream
+  // kernel addresses the output as one buffer: dense rows relative to the tile (any size), scattered ones below 2 GiB.
+  if (stationary && (!epi || (epi->plain && epi->dense_out))) q.kernel = 4;
+  else if (q.variant == 0 && KT <= L2X_MAX_KSTEPS && (!epi || epi->dense_out || epi->y_total < 0x7FFFF000ll)) q.kernel = 3;
+  else q.kernel = q.variant;
+  q.tiles_dp = q.kernel == 3 && !q.balanced ? tiles : tiles - q.rem;  // (the stream kernel is persistent either way: whole tiles only)
+  if (q.kernel == 4) q.grid = tiles < cus ? tiles : cus;  // one workgroup of 8 waves per CU
+  else if (q.kernel == 3) q.grid = q.balanced || tiles > q.G ? q.G : tiles;
+  else q.grid = q.balanced ? q.G : tiles;
   return q;
 }
 }  // namespace
 
 extern "C" {
 
+int onda_conv_l2_variant(int64_t M, int Cout) { return l2_variant_mc(M, Cout, l2_overrides()); }
+
+/* which device kernel onda_conv2d_fwd_l2 launches for a problem: L2Plan.kernel */
+int onda_conv_l2_kernel_id(int64_t M, int Cout, int taps, int Cin) { return l2_plan(M, Cout, taps, Cin, true, 0, false, nullptr).kernel; }
+
 /* rows of the `stats` partials the conv will write for this problem (tile rows + the extra rows of a stream-K remainder) */
-int onda_conv_l2_tiles_m(int64_t M, int Cout, int taps, int Cin) { return l2_schedule(M, Cout, taps, Cin, true).stats_rows_total(); }
+int onda_conv_l2_tiles_m(int64_t M, int Cout, int taps, int Cin) { return l2_plan(M, Cout, taps, Cin, true, 0, false, nullptr).stats_rows_total(); }
 int onda_conv_l2_tiles_m_split(int64_t M, int Cout, int taps, int Cin, int64_t stat_split, int plain_schedule, int* tile_rows) {
-  const L2Schedule q = l2_schedule(M, Cout, taps, Cin, true, stat_split, plain_schedule != 0);
+  const L2Plan q = l2_plan(M, Cout, taps, Cin, true, stat_split, plain_schedule != 0, nullptr);
   if (tile_rows) *tile_rows = q.BM;
   return q.stats_rows_total();
 }
@@ -2340,8 +2358,8 @@ double onda_conv_l2_live_fraction(const OndaConv* c, int with_stats) {
   const long long M = (long long)c->B * c->Ho * c->Wo;
   const int taps = c->kh * c->kw, kcper = c->Cin / 32;
   if (M <= 0 || taps <= 1 || kcper <= 0) return 1.0;
-  const L2Schedule q = l2_schedule(M, c->Cout, taps, c->Cin, true, with_stats ? (long long)c->stat_split : 0, c->plain_schedule != 0);
-  if (onda_conv_l2_kernel_id(M, c->Cout, taps, c->Cin) == 3) return 1.0;
+  const L2Plan q = l2_plan(M, c->Cout, taps, c->Cin, true, with_stats ? (long long)c->stat_split : 0, c->plain_schedule != 0, nullptr);
+  if (q.kernel == 3) return 1.0;
   const int tiles = q.tilesM * q.tilesN, tiles_dp = q.balanced ? tiles - q.rem : tiles;
   long long live_steps = (long long)(tiles - tiles_dp) * taps * kcper;
   for (int tile_m = 0; tile_m * q.tilesN < tiles_dp; ++tile_m) {
@@ -2404,6 +2422,19 @@ static int l2_fwd_impl(const void* xl, int64_t xplane, const float* xamax, const
   if (c->ldy % 4 != 0 || (y && !ONDA_ALIGNED16(y)) || (residual && (c->ldr % 4 != 0 || !ONDA_ALIGNED16(residual)))) return ONDA_EALIGN;
   if (scale && !ONDA_ALIGNED16(scale)) return ONDA_EALIGN;
   if (shift && !ONDA_ALIGNED16(shift)) return ONDA_EALIGN;
+  const long long M = (long long)c->B * c->Ho * c->Wo;
+  ONDA_REQUIRE(M > 0 && M < (1ll << 31));
+  // RowPos packs a tile row's input coordinates of tap (0, 0) into 16 bits each (-32768 = no such row)
+  ONDA_REQUIRE((long long)c->Ho * c->stride + (long long)c->dil * (c->kh - 1) < 32768 &&
+               (long long)c->Wo * c->stride + (long long)c->dil * (c->kw - 1) < 32768 && c->pad < 32768);
+  {  // 32-bit byte offsets inside a tile's WINDOW (x_window: the images its <= 256 rows touch), not inside the tensor
+    const long long img = (long long)c->Hi * c->Wi * c->ldx * 4, per_tile = 256 / ((long long)c->Ho * c->Wo) + 2;
+    ONDA_REQUIRE((per_tile < c->B ? per_tile : c->B) * img < 0x7FFFF000ll);
+  }
+  ONDA_REQUIRE(c->stat_split >= 0 && c->stat_split < M);
+  const size_t limb_elems = (size_t)c->Cout * c->kh * c->kw * c->Cin;  // weight planes are [Cout][taps*Cin]
+  ONDA_REQUIRE(limb_elems * 4 < (1ull << 31));
+
   ConvK k;
   k.x = static_cast<const float*>(xl); k.w = w2; k.y = y; k.scale = scale; k.shift = shift; k.res = residual; k.stats = stats; k.ws = ws;
   k.amax = yamax;
@@ -2420,118 +2451,81 @@ static int l2_fwd_impl(const void* xl, int64_t xplane, const float* xamax, const
     k.res_amax = lo->res_amax;
     k.res_true = lo->res_true ? lo->res_true : lo->res_amax;
   }
-  k.skip_dead_taps = getenv("ONDA_L2A_WKB") ? 78 : 1;
+  k.skip_dead_taps = 1;
   k.late_issue = 1;
   static const int stamp_on = getenv("ONDA_L2X_STAMP") ? atoi(getenv("ONDA_L2X_STAMP")) : 0;
-  if (stamp_on)  // the last 64 KiB of the workspace (beyond anything the schedules use: checked below)
+  if (stamp_on)  // the last 64 KiB of the workspace (beyond anything the schedules use: l2_plan's workspace bound)
     k.stamps = reinterpret_cast<unsigned long long*>(ws + onda_conv_ws_floats()) - 1024 * 32;
   k.c = *c;
-  const long long M = (long long)c->B * c->Ho * c->Wo;
-  ONDA_REQUIRE(M > 0 && M < (1ll << 31));
-  // RowPos packs a tile row's input coordinates of tap (0, 0) into 16 bits each (-32768 = no such row)
-  ONDA_REQUIRE((long long)c->Ho * c->stride + (long long)c->dil * (c->kh - 1) < 32768 &&
-               (long long)c->Wo * c->stride + (long long)c->dil * (c->kw - 1) < 32768 && c->pad < 32768);
-  const long long x_total = (long long)c->B * c->Hi * c->Wi * c->ldx * 4;  // limb rows: 4 bytes per element
-  {  // 32-bit byte offsets inside a tile's WINDOW (x_window: the images its <= 256 rows touch), not inside the tensor
-    const long long img = (long long)c->Hi * c->Wi * c->ldx * 4, per_tile = 256 / ((long long)c->Ho * c->Wo) + 2;
-    ONDA_REQUIRE((per_tile < c->B ? per_tile : c->B) * img < 0x7FFFF000ll);
-  }
-  k.x_total = x_total;
+  k.x_total = (long long)c->B * c->Hi * c->Wi * c->ldx * 4;  // limb rows: 4 bytes per element
   k.M = (int)M;
   k.taps = c->kh * c->kw;
   k.kcper = c->Cin / 32;
-  ONDA_REQUIRE(c->stat_split >= 0 && c->stat_split < M);
-  const L2Schedule q = l2_schedule(M, c->Cout, k.taps, c->Cin, true, stats ? (long long)c->stat_split : 0, c->plain_schedule != 0);
+
+  // the output as a buffer: last byte any tile can store (dense rows of ldy floats; scattered stride-2 gradients included)
+  const bool dense_out = c->out_os == 1 && c->Hf == c->Ho && c->Wf == c->Wo;
+  const long long y_rows = (long long)c->B * (dense_out ? (long long)c->Ho * c->Wo : (long long)c->Hf * c->Wf);
+  const long long y_total = ((y_rows - 1) * c->ldy + c->Cout) * 4;
+  const L2Epilogue epi = {lo == nullptr && !scale && !shift && !residual && !c->relu && !yamax, dense_out, y_total};
+  const L2Plan q = l2_plan(M, c->Cout, k.taps, c->Cin, true, stats ? (long long)c->stat_split : 0, c->plain_schedule != 0, &epi);
+  ONDA_REQUIRE(q.variant >= 0 && q.variant <= 2);  // (an ONDA_L2_VARIANT that names no tile)
   k.tilesM = q.tilesM;
   k.tilesN = q.tilesN;
-  const size_t limb_elems = (size_t)c->Cout * k.taps * c->Cin;  // weight planes are [Cout][taps*Cin]
-  ONDA_REQUIRE(limb_elems * 4 < (1ull << 31));
+  k.tiles_dp = q.tiles_dp;
+
   const unsigned x_bytes = 0, w_bytes = (unsigned)(limb_elems * 4);  // (x: ConvK.x_total, windows per tile)
   const unsigned xpl = 0, wpl = 0;  // (unused by the kernels since the limbs share a row)
-  const int tiles = k.tilesM * k.tilesN;
-  k.tiles_dp = tiles - q.rem;
   hipStream_t st = ONDA_STREAM(s);
-#define L2_LAUNCH(WM_, WN_, ST_, OCC_)                                                                                       \
+#define L2_FIXUP(BM_, BN_) \
+  hipLaunchKernelGGL((conv_l2_fixup_kernel<BM_, BN_>), dim3(q.rem_rows() * q.tilesN, q.sub), dim3(256), 0, st, k, q.G, q.tilesM)
+#define L2_LAUNCH(WM_, WN_, ST_, OCC_, ...)                                                                                  \
   do {                                                                                                                       \
     if (q.balanced) {                                                                                                        \
-      hipLaunchKernelGGL((conv_l2_kernel<WM_, WN_, ST_, OCC_, true>), dim3(q.G), dim3(WM_ * WN_ * 64), 0, st, k, xpl, wpl, x_bytes, \
-                         w_bytes, xamax, wamax);                                                                            \
-      hipLaunchKernelGGL((conv_l2_fixup_kernel<64 * WM_, 64 * WN_>), dim3(q.rem_rows() * q.tilesN, q.sub), dim3(256), 0, st, k, q.G, \
-                         q.tilesM);                                                                                           \
+      hipLaunchKernelGGL((conv_l2_kernel<WM_, WN_, ST_, OCC_, true, ##__VA_ARGS__>), dim3(q.grid), dim3(WM_ * WN_ * 64), 0, st, k, xpl, \
+                         wpl, x_bytes, w_bytes, xamax, wamax);                                                               \
+      L2_FIXUP(64 * WM_, 64 * WN_);                                                                                          \
     } else {                                                                                                                 \
-      hipLaunchKernelGGL((conv_l2_kernel<WM_, WN_, ST_, OCC_, false>), dim3(tiles), dim3(WM_ * WN_ * 64), 0, st, k, xpl, wpl,    \
-                         x_bytes, w_bytes, xamax, wamax);                                                                   \
+      hipLaunchKernelGGL((conv_l2_kernel<WM_, WN_, ST_, OCC_, false, ##__VA_ARGS__>), dim3(q.grid), dim3(WM_ * WN_ * 64), 0, st, k, xpl, \
+                         wpl, x_bytes, w_bytes, xamax, wamax);                                                               \
     }                                                                                                                        \
   } while (0)
-  // the output as a buffer: last byte any tile can store (dense rows of ldy floats; scattered stride-2 gradients included)
-  const long long y_rows = (long long)c->B * (c->out_os == 1 && c->Hf == c->Ho && c->Wf == c->Wo ? (long long)c->Ho * c->Wo : (long long)c->Hf * c->Wf);
-  const long long y_total = ((y_rows - 1) * c->ldy + c->Cout) * 4;
-  const bool dense_out = c->out_os == 1 && c->Hf == c->Ho && c->Wf == c->Wo;  // (buffer stores relative to the tile: any size)
-  // conv_l2a_kernel takes the plain epilogue (with or without statistics).  Everything else -- scale / shift / residual / ReLU /
-  // max|y|, limb-row outputs, scattered outputs -- runs on the 128 x 128 tile kernel: same statistic rows, no stream-K remainder.
-  const bool plain_epi = lo == nullptr && scale == nullptr && shift == nullptr && !c->relu && yamax == nullptr;
-  const int epi = plain_epi && residual == nullptr ? 0 : -1;
-  if (q.stationary && dense_out && epi >= 0) {
-    // 1 x 1, Cin 64 / 128 / 256: the rows in registers, the weights streamed (conv_l2a_kernel)
-    ONDA_REQUIRE(c->pad == 0 && (c->stride == 1 || (c->Hi >= (c->Ho - 1) * c->stride + 1 && c->Wi >= (c->Wo - 1) * c->stride + 1)));
-    const long long items = (long long)k.tilesM * k.tilesN;
-    const int cus = conv_resident_workgroups() / 2;
-    const int slots = cus;  // one workgroup of 8 waves per CU
-    const int grid = (int)(items < slots ? items : slots);
-#define L2A_LAUNCH(KB_, NST_, A2L_, EPI_) \
-  hipLaunchKernelGGL((conv_l2a_kernel<KB_, NST_, A2L_, EPI_>), dim3(grid), dim3(512), 0, st, k, w_bytes, (unsigned)y_total, xamax, wamax)
-    if (c->Cin == 256) L2A_LAUNCH(8, 3, true, 0);
-    else if (c->Cin == 128) L2A_LAUNCH(4, 3, false, 0);
-    else L2A_LAUNCH(2, 3, false, 0);
-#undef L2A_LAUNCH
-    return ONDA_LAUNCH_RESULT();
-  }
-  // short K loops (1 x 1 convolutions up to 1024 input channels) gain 6-17 % from the continuous stream; long ones lose
-  // ~4 % against the slot-staggered kernel, whose per-tile start / end they amortise anyway (measured per shape, one process)
-  const bool short_k = k.taps * k.kcper <= l2x_max_ksteps();
-  if (short_k && q.variant == 0 && (dense_out || y_total < 0x7FFFF000ll)) {
-    if (!q.balanced) k.tiles_dp = tiles;  // persistent either way: whole tiles only
-    const int grid = tiles < q.G ? tiles : q.G;
-    hipLaunchKernelGGL((conv_l2x_kernel<4, 2, 3, 2>), dim3(q.balanced ? q.G : grid), dim3(512), 0, st, k, xpl, wpl, x_bytes, w_bytes,
-                       (unsigned)y_total, xamax, wamax);
-    if (q.balanced)
-      hipLaunchKernelGGL((conv_l2_fixup_kernel<256, 128>), dim3(q.rem_rows() * q.tilesN, q.sub), dim3(256), 0, st, k, q.G, q.tilesM);
-    return ONDA_LAUNCH_RESULT();
-  }
-#ifdef ONDA_L2_ABLATIONS  // measurement builds only (tools/README.md): ONDA_L2_DBG = 1 no vmcnt waits, 2 no DMA in the K loop,
-  {                       // 7 half of the LDS fragment reads, 8 none, 9 half of the DMA instructions, 10 neither DMA nor reads, 11 nor barriers -- wrong results, valid timings; 12 = stamps of one K-step's slots into the workspace
-                          // (tools/l2_slot_stamps.py)
-    static const int dbg = getenv("ONDA_L2_DBG") ? atoi(getenv("ONDA_L2_DBG")) : 0;
-#define L2_DBG_LAUNCH(D_)                                                                                                      \
-  do {                                                                                                                         \
-    if (q.balanced) {                                                                                                          \
-      hipLaunchKernelGGL((conv_l2_kernel<4, 2, 3, 2, true, D_>), dim3(q.G), dim3(512), 0, st, k, xpl, wpl, x_bytes, w_bytes, xamax, \
-                         wamax);                                                                                               \
-      hipLaunchKernelGGL((conv_l2_fixup_kernel<256, 128>), dim3(q.rem_rows() * q.tilesN, q.sub), dim3(256), 0, st, k, q.G, q.tilesM); \
-    } else {                                                                                                                   \
-      hipLaunchKernelGGL((conv_l2_kernel<4, 2, 3, 2, false, D_>), dim3(tiles), dim3(512), 0, st, k, xpl, wpl, x_bytes, w_bytes, xamax, \
-                         wamax);                                                                                               \
-    }                                                                                                                          \
-    return ONDA_LAUNCH_RESULT();                                                                                               \
-  } while (0)
-    if (q.variant == 0 && dbg == 5) L2_DBG_LAUNCH(5);  // per-workgroup ticks of set-up / K loop / epilogue into the workspace (tools/l2_tile_stamps.py)
-    if (q.variant == 0 && dbg == 1) L2_DBG_LAUNCH(1);
-    if (q.variant == 0 && dbg == 2) L2_DBG_LAUNCH(2);
-    if (q.variant == 0 && dbg == 7) L2_DBG_LAUNCH(7);
-    if (q.variant == 0 && dbg == 8) L2_DBG_LAUNCH(8);
-    if (q.variant == 0 && dbg == 9) L2_DBG_LAUNCH(9);
-    if (q.variant == 0 && dbg == 10) L2_DBG_LAUNCH(10);
-    if (q.variant == 0 && dbg == 11) L2_DBG_LAUNCH(11);
-    if (q.variant == 0 && dbg == 12) L2_DBG_LAUNCH(12);
-#undef L2_DBG_LAUNCH
-  }
+#define L2A_LAUNCH(KB_, NST_, A2L_) \
+  hipLaunchKernelGGL((conv_l2a_kernel<KB_, NST_, A2L_, 0>), dim3(q.grid), dim3(512), 0, st, k, w_bytes, (unsigned)y_total, xamax, wamax)
+  switch (q.kernel) {
+    case 0:
+#ifdef ONDA_L2_ABLATIONS
+    {  // measurement builds only (tools/README.md): ONDA_L2_DBG = 1 no vmcnt waits, 2 no DMA in the K loop, 7 half of the LDS
+       // fragment reads, 8 none, 9 half of the DMA instructions, 10 neither DMA nor reads, 11 nor barriers -- wrong results, valid
+       // timings; 12 = stamps of one K-step's slots into the workspace (tools/l2_slot_stamps.py); 5 = per-workgroup ticks of
+       // set-up / K loop / epilogue into the workspace (tools/l2_tile_stamps.py)
+      static const int dbg = getenv("ONDA_L2_DBG") ? atoi(getenv("ONDA_L2_DBG")) : 0;
+#define L2_DBG_CASE(D_) case D_: L2_LAUNCH(4, 2, 3, 2, D_); return ONDA_LAUNCH_RESULT()
+      switch (dbg) {
+        L2_DBG_CASE(1); L2_DBG_CASE(2); L2_DBG_CASE(5); L2_DBG_CASE(7); L2_DBG_CASE(8); L2_DBG_CASE(9); L2_DBG_CASE(10); L2_DBG_CASE(11);
+        L2_DBG_CASE(12);
+      }
+#undef L2_DBG_CASE
+    }
 #endif
-  if (q.variant == 0) L2_LAUNCH(4, 2, 3, 2);
-  else if (q.variant == 1 && l2_small_ring2()) L2_LAUNCH(2, 2, 2, 2);
-  else if (q.variant == 1) L2_LAUNCH(2, 2, 3, 1);
-  else if (l2_small_ring2()) L2_LAUNCH(4, 1, 2, 2);
-  else L2_LAUNCH(4, 1, 3, 1);
+      L2_LAUNCH(4, 2, 3, 2);
+      break;
+    case 1: L2_LAUNCH(2, 2, 2, 2); break;
+    case 2: L2_LAUNCH(4, 1, 2, 2); break;
+    case 3:  // the continuous K-step stream: persistent workgroups, whole tiles, then the remainder's pieces
+      hipLaunchKernelGGL((conv_l2x_kernel<4, 2, 3, 2>), dim3(q.grid), dim3(512), 0, st, k, xpl, wpl, x_bytes, w_bytes, (unsigned)y_total,
+                         xamax, wamax);
+      if (q.balanced) L2_FIXUP(256, 128);
+      break;
+    case 4:  // 1 x 1, Cin 64 / 128 / 256: the rows in registers, the weights streamed
+      ONDA_REQUIRE(c->pad == 0 && (c->stride == 1 || (c->Hi >= (c->Ho - 1) * c->stride + 1 && c->Wi >= (c->Wo - 1) * c->stride + 1)));
+      if (c->Cin == 256) L2A_LAUNCH(8, 3, true);
+      else if (c->Cin == 128) L2A_LAUNCH(4, 3, false);
+      else L2A_LAUNCH(2, 3, false);
+      break;
+  }
+#undef L2A_LAUNCH
 #undef L2_LAUNCH
+#undef L2_FIXUP
   return ONDA_LAUNCH_RESULT();
 }
 

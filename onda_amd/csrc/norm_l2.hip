@@ -235,7 +235,7 @@ __device__ __forceinline__ void reduce_rows16(const float* __restrict__ partials
 // split is not a multiple of bm -- every feature grid of this network leaves 4 rows over) is counted whole with group 1
 // and corrected by the sums over its group-0 rows, read straight from the conv output y (a few rows x 16 channels per
 // workgroup): group 0 adds them, group 1 subtracts them.  Extrema only have to BOUND a group's: group 1 keeps the whole
-// row's.  (The host guarantees that the straddling tile is not a stream-K remainder tile: csrc/conv_l2.hip, l2_schedule.)
+// row's.  (The host guarantees that the straddling tile is not a stream-K remainder tile: csrc/conv_l2.hip, l2_plan.)
 // run_group: the group whose statistics move the running buffers (-1: none).
 struct BnFinalizeArgs {
   const float* partials;

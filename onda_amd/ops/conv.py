@@ -1,15 +1,14 @@
 """Convolutions: weight packers, gradient sinks, forward / data gradient / weight gradient launches (f16x2 pre-split and exact
 fp32), the per-model packer, the autograd functions of the convs and the stem."""
 import ctypes
-import os
 from ctypes import byref
 
 import torch
 
 from .. import _lib
-from .._lib import OndaConv, OndaLimbOut, call, query
+from .._lib import OndaLimbOut, call, query
 from . import _state
-from ._state import BN_EPS, GN_EPS, GN_GROUPS, HEAD_PAD, STEM_K
+from ._state import STEM_K
 from .core import _conv_ws, _desc, _group_split, _l2_name, _launch, _p, _require_cuda, _stream, as_nhwc, conv_out_size, nhwc_ld
 from .limbs import H2Weight, Limbs, amax_slot, is_limb_only, known_amax, limb_only, limbs_of, tag_amax
 from .tables import _table
@@ -72,8 +71,6 @@ class GradSink:
         self.buf, self.pending = None, 0
 
 
-
-
 def share_grad(x):
     """Mark `x` (about to be consumed by several of this module's Functions, and by nothing else) for GradSink."""
     if _state.SHARE_GRADS and torch.is_grad_enabled() and x.requires_grad and getattr(x, "_onda_sink", None) is None:
@@ -108,6 +105,23 @@ def _sink_give(sink, grad, owned):
     return out
 
 
+def _l2_profile(kind, d, with_stats, tag_dims):
+    """Kernel name, flop count, tag and issued-share callable of a pre-split forward / data-gradient launch described by `d`:
+    the first two arguments and the keywords of `_launch`.  tag_dims: (M, Cout, Cin, k, stride, dil) as the caller's conv has them.
+    (The flops are those of the caller's conv: a data gradient counts the pixels of dy, the input of the conv that computes it.)"""
+    taps, pixels = d.kh * d.kw, d.B * (d.Hi * d.Wi if kind == "dgrad" else d.Ho * d.Wo)
+    return ((_l2_name(d.B * d.Ho * d.Wo, d.Cout, taps, d.Cin), 2.0 * pixels * d.Cout * taps * d.Cin),
+            dict(tag=(kind,) + tuple(tag_dims), issued=lambda: query("onda_conv_l2_live_fraction", byref(d), with_stats)))
+
+
+def _launch_l2(kind, xl, wp, out, d, *, scale=None, shift=None, residual=None, stats=None, stats_rows=2, yamax=None, with_stats=0,
+               tag_dims):
+    """One onda_conv2d_fwd_l2 launch: limb planes `xl` times the packed weight `wp` into `out`, as `d` describes it."""
+    head, kw = _l2_profile(kind, d, with_stats, tag_dims)
+    _launch(*head, "onda_conv2d_fwd_l2", _p(xl.planes), xl.plane, _p(xl.amax), _p(wp.limbs), _p(wp.amax), _p(out), _p(scale),
+            _p(shift), _p(residual), _p(stats), stats_rows, _p(_conv_ws(out.device)), _p(yamax), byref(d), _stream(), **kw)
+
+
 def conv_forward(x, wp, k, stride, dil, pad, cout, out=None, scale=None, shift=None, residual=None, relu=False,
                  want_stats=False, limb_out=None):
     """x NHWC view, wp packed [cout][k*k*Cin].  Returns (y, stats partials or None, tiles).
@@ -131,10 +145,9 @@ def conv_forward(x, wp, k, stride, dil, pad, cout, out=None, scale=None, shift=N
         lo = OndaLimbOut(_p(planes), M * cout, _p(bound), _p(true), _p(limb_out), _p(xl.true_amax),
                          _p(res.planes) if res is not None else None, res.plane if res is not None else 0,
                          _p(res.amax) if res is not None else None, _p(res.true_amax) if res is not None else None)
-        _launch(_l2_name(M, cout, k * k, Cin), 2.0 * M * cout * k * k * Cin,
-                "onda_conv2d_fwd_l2_limbs", _p(xl.planes), xl.plane, _p(xl.amax), _p(wp.limbs), _p(wp.amax), _p(scale), _p(shift),
-                byref(lo), _p(_conv_ws(dev)), byref(d), _stream(), tag=("fwd", M, cout, Cin, k, stride, dil),
-                issued=lambda: query("onda_conv_l2_live_fraction", byref(d), 0))
+        head, kw = _l2_profile("fwd", d, 0, (M, cout, Cin, k, stride, dil))
+        _launch(*head, "onda_conv2d_fwd_l2_limbs", _p(xl.planes), xl.plane, _p(xl.amax), _p(wp.limbs), _p(wp.amax), _p(scale),
+                _p(shift), byref(lo), _p(_conv_ws(dev)), byref(d), _stream(), **kw)
         return limb_only((B, Ho, Wo, cout), dev, Limbs(planes, bound, cout, M * cout, true_amax=true)), None, 0
     if out is None:
         out = torch.empty(B, Ho, Wo, cout, device=x.device, dtype=torch.float32)
@@ -165,11 +178,8 @@ def conv_forward(x, wp, k, stride, dil, pad, cout, out=None, scale=None, shift=N
         xl = limbs_of(x)
         d.ldx = xl.ld
         yamax = amax_slot(x.device) if (scale is not None or relu) else None
-        _launch(_l2_name(B * Ho * Wo, cout, k * k, Cin), 2.0 * B * Ho * Wo * cout * k * k * Cin,
-                "onda_conv2d_fwd_l2", _p(xl.planes), xl.plane, _p(xl.amax), _p(wp.limbs), _p(wp.amax), _p(out), _p(scale),
-                _p(shift), _p(residual), _p(stats), stats_rows, _p(_conv_ws(x.device)), _p(yamax), byref(d), _stream(),
-                tag=("fwd", B * Ho * Wo, cout, Cin, k, stride, dil),
-                issued=lambda: query("onda_conv_l2_live_fraction", byref(d), int(stats is not None)))
+        _launch_l2("fwd", xl, wp, out, d, scale=scale, shift=shift, residual=residual, stats=stats, stats_rows=stats_rows,
+                   yamax=yamax, with_stats=int(stats is not None), tag_dims=(B * Ho * Wo, cout, Cin, k, stride, dil))
         if yamax is not None:
             tag_amax(out, yamax)
         return out, stats, tiles
@@ -197,11 +207,7 @@ def conv_dgrad(dy, wpd, k, stride, dil, pad, cin, in_hw, accumulate=None):
         d = _desc(B, Ho, Wo, Co, Hi, Wi, cin, k, 1, dil, dil * (k - 1) - pad, ldy, cin, cin)
         dyl = limbs_of(dy)
         d.ldx = dyl.ld
-        _launch(_l2_name(B * Hi * Wi, cin, k * k, Co), 2.0 * B * Ho * Wo * cin * k * k * Co,
-                "onda_conv2d_fwd_l2", _p(dyl.planes), dyl.plane, _p(dyl.amax), _p(wpd.limbs), _p(wpd.amax), _p(accumulate), None,
-                None, _p(accumulate), None, 2, _p(_conv_ws(dy.device)), None, byref(d), _stream(),
-                tag=("dgrad", B * Hi * Wi, cin, Co, k, stride, dil),
-                issued=lambda: query("onda_conv_l2_live_fraction", byref(d), 0))
+        _launch_l2("dgrad", dyl, wpd, accumulate, d, residual=accumulate, tag_dims=(B * Hi * Wi, cin, Co, k, stride, dil))
         return accumulate
     if stride == 1:
         dx = torch.empty(B, Hi, Wi, cin, device=dy.device, dtype=torch.float32)
@@ -214,11 +220,7 @@ def conv_dgrad(dy, wpd, k, stride, dil, pad, cin, in_hw, accumulate=None):
     if _use_l2(wpd, Co):
         dyl = limbs_of(dy)
         d.ldx = dyl.ld
-        Mo = B * Ho * Wo if stride != 1 else B * Hi * Wi
-        _launch(_l2_name(Mo, cin, k * k, Co), 2.0 * B * Ho * Wo * cin * k * k * Co,
-                "onda_conv2d_fwd_l2", _p(dyl.planes), dyl.plane, _p(dyl.amax), _p(wpd.limbs), _p(wpd.amax), _p(dx), None, None,
-                None, None, 2, _p(_conv_ws(dy.device)), None, byref(d), _stream(),
-                tag=("dgrad", Mo, cin, Co, k, stride, dil), issued=lambda: query("onda_conv_l2_live_fraction", byref(d), 0))
+        _launch_l2("dgrad", dyl, wpd, dx, d, tag_dims=(B * Ho * Wo if stride != 1 else B * Hi * Wi, cin, Co, k, stride, dil))
         return dx
     if is_limb_only(dy):
         raise RuntimeError("onda_amd: a limb-only gradient reached a data-gradient kernel that does not take limb planes")
@@ -290,10 +292,10 @@ def _wgrad_pixel_table(d, device):
     d.pix_table, d.pix_stride = hit[0].data_ptr(), hit[2]
 
 
-def conv_wgrad(x, dy, k, stride, dil, pad, cout_real, cin_real, flat_k=0, into=None, xscale=None, xlimbs=None):
+def conv_wgrad(x, dy, k, stride, dil, pad, cout_real, cin_real, flat_k=0, into=None, xlimbs=None):
     """Weight gradient in OIHW.  x NHWC input of the conv, dy NHWC output gradient.  With `into`
     (an existing contiguous gradient tensor) the result is ADDED to it and None is returned.
-    xscale: the per-tensor scale of x when the forward pass already computed it ("f16x2" mode)."""
+    xlimbs: the limb planes of x when the forward pass already made them ("f16x2" mode)."""
     B, Hi, Wi, Cin = x.shape
     _, Ho, Wo, Co = dy.shape
     taps = k * k
@@ -314,14 +316,10 @@ def conv_wgrad(x, dy, k, stride, dil, pad, cout_real, cin_real, flat_k=0, into=N
                 dyl.ld, sk, byref(d), _stream(), tag=("wgrad", M, Co, Cin, k, stride, dil, sk),
                 issued=lambda: query("onda_conv_wgrad_l2_live_fraction", byref(d), sk))
     else:
-        _wgrad_other(x, dy, slabs, sk, d, M, Co, taps, Cin, k, stride, dil)
+        _launch("conv_wgrad_kernel<%s>" % ("128,128" if (Co > 64 and Cin > 64) else "64,64"), 2.0 * M * Co * taps * Cin,
+                "onda_conv2d_wgrad", _p(x), _p(dy), _p(slabs), nhwc_ld(dy), sk, byref(d), _stream(),
+                tag=("wgrad", M, Co, Cin, k, stride, dil, sk))
     return _wgrad_finish(slabs, into, sk, Co, taps, Cin, cout_real, cin_real, flat_k, k, x.device)
-
-
-def _wgrad_other(x, dy, slabs, sk, d, M, Co, taps, Cin, k, stride, dil):
-    _launch("conv_wgrad_kernel<%s>" % ("128,128" if (Co > 64 and Cin > 64) else "64,64"), 2.0 * M * Co * taps * Cin,
-            "onda_conv2d_wgrad", _p(x), _p(dy), _p(slabs), nhwc_ld(dy), sk, byref(d), _stream(),
-            tag=("wgrad", M, Co, Cin, k, stride, dil, sk))
 
 
 def _wgrad_finish(slabs, into, sk, Co, taps, Cin, cout_real, cin_real, flat_k, k, device):
@@ -444,9 +442,8 @@ class Conv2dFn(torch.autograd.Function):
         wp = cache.get_fwd(weight, cout_pad)
         y, stats, _tiles = conv_forward(x, wp, k, stride, dil, pad, co, shift=_pad_vec(bias, co), want_stats=want_stats)
         ctx.save_for_backward(x, weight)
-        ctx.xscale = known_amax(x)  # "f16x2": max|x| of the input, reused by the weight gradient
         hit = getattr(x, "_onda_limbs", None)
-        ctx.xlimbs = hit[1] if hit is not None and hit[0] == x._version else None  # ... and its limb planes
+        ctx.xlimbs = hit[1] if hit is not None and hit[0] == x._version else None  # "f16x2": the input's limb planes, reused by the weight gradient
         ctx.weight_param = weight  # the Parameter itself: its .grad is the accumulation target
         ctx.sink = _sink_of(x) if ctx.needs_input_grad[0] else None
         ctx.cache, ctx.geom, ctx.has_bias = cache, (k, stride, dil, pad, cout, cin, cout_pad), bias is not None
@@ -476,7 +473,7 @@ class Conv2dFn(torch.autograd.Function):
                 dx = _sink_give(sink, conv_dgrad(dy, wpd, k, stride, dil, pad, cin, x.shape[1:3]), True)
         if ctx.needs_input_grad[1]:
             into = _accumulate_target(ctx.weight_param)
-            dw = conv_wgrad(x, dy, k, stride, dil, pad, cout, cin, into=into, xscale=ctx.xscale, xlimbs=ctx.xlimbs)
+            dw = conv_wgrad(x, dy, k, stride, dil, pad, cout, cin, into=into, xlimbs=ctx.xlimbs)
             if into is not None and _state.GRAD_READY is not None:
                 _state.GRAD_READY(ctx.weight_param)
         if ctx.has_bias and ctx.needs_input_grad[2]:
@@ -571,5 +568,3 @@ def stem_eval(x_nchw, weight, cache, scale, shift):
         col = stem_patches(x_nchw, Ho, Wo, _use_l2(wp, STEM_K))
         y, _, _ = conv_forward(col, wp, 1, 1, 1, 0, weight.shape[0], scale=scale, shift=shift, relu=True)
     return y
-
-

@@ -1,15 +1,9 @@
 """Launch plumbing of the operator layer: the current stream, profiled launches, NHWC views, conv descriptors, device predicates,
 row groups, the stream-K workspace."""
-import ctypes
-import os
-from ctypes import byref
-
 import torch
 
-from .. import _lib
-from .._lib import OndaConv, OndaLimbOut, call, query
+from .._lib import OndaConv, call, query
 from . import _state
-from ._state import BN_EPS, GN_EPS, GN_GROUPS, HEAD_PAD, STEM_K
 
 
 def _stream():
@@ -85,8 +79,6 @@ def conv_out_size(n, k, stride, dil, pad):
     return (n + 2 * pad - dil * (k - 1) - 1) // stride + 1
 
 
-
-
 class predicated:
     """``with ops.predicated(flag):`` -- no-grad forward passes only (nothing in a backward pass reads the flag)."""
 
@@ -109,8 +101,6 @@ def predicates_supported():
 def _desc(B, Hi, Wi, Cin, Ho, Wo, Cout, k, stride, dil, pad, ldx, ldy, ldr=0, out_os=1, Hf=None, Wf=None, relu=0, split=0):
     return OndaConv(B, Hi, Wi, Cin, Ho, Wo, Cout, k, k, stride, dil, pad, ldx, ldy, ldr, out_os,
                     Ho if Hf is None else Hf, Wo if Wf is None else Wf, int(relu), _p(_state.PREDICATE), int(split), 0)
-
-
 
 
 class row_groups:
@@ -146,5 +136,3 @@ def _conv_ws(device):
     if ws is None:
         ws = _CONV_WS[key] = torch.empty(query("onda_conv_ws_floats"), device=device, dtype=torch.float32)
     return ws
-
-

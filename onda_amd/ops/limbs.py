@@ -153,9 +153,9 @@ def limbs_of(x):
 
 
 def _stat_tile_rows(stats):
-    """GEMM rows one row of a conv's statistic partials covers (256 or 128: l2_schedule's tile height, recorded by
+    """GEMM rows one row of a conv's statistic partials covers (256 or 128: l2_plan's tile height, recorded by
     conv_forward).  Two row groups split their partials by it; there is no way to re-derive it from (M, C) alone -- short K
-    loops run 128-row tiles (l2_variant_k) -- so a partial table that lost the attribute (detached, cloned, re-wrapped) is an
+    loops run 128-row tiles (l2_plan) -- so a partial table that lost the attribute (detached, cloned, re-wrapped) is an
     error, not a guess (round-5 advisor)."""
     rows = getattr(stats, "_onda_tile_rows", None)
     if not rows:

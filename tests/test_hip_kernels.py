@@ -230,6 +230,75 @@ def test_activation_stationary_conv_is_the_tile_kernel_bit_for_bit(case, epilogu
         os.environ.pop("ONDA_L2_STATIONARY", None)
 
 
+L2_PLAN_CASES = [
+    # kernel id, cin, cout, B, H, W   (1 x 1 convolutions, the smallest that select each device kernel: tests/golden/l2_plan.json)
+    (0, 1056, 256, 2, 99, 130),   # 101 x 2 tiles of 256 x 128 (the last tile row 140 rows), 33 K-steps: past the stream kernel's 32
+    (1, 128, 160, 2, 9, 17),      # 128 x 128 tiles, the second column tile a quarter full
+    (2, 64, 64, 2, 9, 17),        # 256 x 64 tiles
+    (3, 512, 256, 2, 105, 170),   # 16 K-steps: the continuous stream; 280 tiles = one round + a stream-K remainder (512 statistic rows)
+    (4, 128, 256, 1, 9, 17),      # activation-stationary (switched on for the case)
+]
+
+
+@pytest.mark.parametrize("case", L2_PLAN_CASES, ids=lambda c: "id%d" % c[0])
+def test_l2_launch_follows_its_plan(case, monkeypatch):
+    """One problem per device kernel of the pre-split conv (csrc/conv_l2.hip l2_plan), in each epilogue the launch tells apart:
+    plain + statistics, folded BatchNorm + residual + ReLU, limb-row output, and the scattered stride-2 data gradient (dy and the
+    transposed weight chosen so that it is the SAME (M, Cout, K) problem).  The launch is recorded under the kernel the host
+    query names, the statistics have the rows the query promises and sum to the reference's, and every output meets the
+    file's conv bound against F.conv2d."""
+    import ctypes
+    from onda_amd import ops
+    from onda_amd._lib import query
+    kid, cin, cout, B, H, W = case
+    M = B * H * W
+    if kid == 4:
+        monkeypatch.setenv("ONDA_L2_STATIONARY", "1")
+    monkeypatch.setattr(ops._state, "CONV_MODE", "f16x2")
+    monkeypatch.setattr(ops._state, "PROFILE", [])
+    assert query("onda_conv_l2_kernel_id", M, cout, 1, cin) == kid
+    name = ops.core._L2_KERNELS[kid]
+    g = torch.Generator().manual_seed(kid)
+    x = torch.randn(B, cin, H, W, generator=g)
+    w = torch.randn(cout, cin, 1, 1, generator=g) / cin ** 0.5
+    sc, sh = torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g)
+    res = torch.randn(B, cout, H, W, generator=g)
+    ref = F.conv2d(x, w)
+    affine = ref * sc[None, :, None, None] + sh[None, :, None, None]
+    xd, wd, scd, shd = nhwc(x).to(DEV), w.to(DEV), sc.to(DEV), sh.to(DEV)
+    wp = ops.pack_weight_fwd(wd)
+
+    def launched(kind):
+        torch.cuda.synchronize()
+        got = [(e[0], e[4][:4]) for e in ops._state.PROFILE if e[4] and e[4][0] in ("fwd", "dgrad")]
+        del ops._state.PROFILE[:]
+        assert got == [(name, (kind, M, cout, cin))], got
+
+    y, stats, tiles = ops.conv_forward(xd, wp, 1, 1, 1, 0, cout, want_stats=4)
+    launched("fwd")
+    rows = ctypes.c_int(0)
+    assert stats.shape[0] == tiles == query("onda_conv_l2_tiles_m_split", M, cout, 1, cin, 0, 0, ctypes.byref(rows))
+    assert stats._onda_tile_rows == rows.value == (128 if kid in (1, 4) else 256)
+    close(nchw(y), ref, 2e-5, "plain")
+    close(stats[:, 0].sum(0), ref.sum((0, 2, 3)), 1e-4, "stats sum")
+    close(stats[:, 1].sum(0), (ref ** 2).sum((0, 2, 3)), 1e-4, "stats sumsq")
+
+    y, _, _ = ops.conv_forward(xd, wp, 1, 1, 1, 0, cout, scale=scd, shift=shd, residual=nhwc(res).to(DEV), relu=True)
+    launched("fwd")
+    close(nchw(y), F.relu(affine + res), 2e-5, "affine + residual + ReLU")
+
+    y, _, _ = ops.conv_forward(xd, wp, 1, 1, 1, 0, cout, scale=scd, shift=shd, relu=True, limb_out=ops.fold_bounds(wd, scd, shd))
+    launched("fwd")
+    close(nchw(ops.materialize(y)), F.relu(affine), 2e-5, "limb rows")
+
+    # the data gradient of a stride-2 1 x 1 conv with cout -> cin channels swapped: dx[2h, 2w] = dy[h, w] . W, zero elsewhere
+    wpd = ops.pack_weight_dgrad(wd.permute(1, 0, 2, 3).contiguous())
+    dx = ops.conv_dgrad(xd, wpd, 1, 2, 1, 0, cout, (2 * H - 1, 2 * W - 1))
+    launched("dgrad")
+    close(nchw(dx[:, ::2, ::2]), ref, 2e-5, "scattered data gradient")
+    assert dx[:, 1::2].abs().max().item() == 0 and dx[:, :, 1::2].abs().max().item() == 0
+
+
 @pytest.mark.parametrize("case", CONV_CASES, ids=lambda c: "x".join(map(str, c[:6])))
 def test_conv_fwd_bwd(case, conv_mode):
     from onda_amd import ops
