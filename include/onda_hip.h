@@ -341,6 +341,17 @@ int onda_upsample_ce_fwd(const float* logits, int ldl, const uint8_t* labels, fl
 int64_t onda_upsample_ce_bwd_ws(int B, int w, int K, int H);  /* floats of `ws` for the backward pass */
 int onda_upsample_ce_bwd(const float* logits, int ldl, const uint8_t* labels, const float* result, const float* gscale, float w_ce,
                          float* dlogits, float* ws, int B, int h, int w, int K, int H, int W, onda_stream_t s);
+/* ADVENT's entropy map (advent_da.py:94-128, func.py:71-74): out f32[B,K,H,W] = prob_2_entropy(softmax(interp(logits), 1)),
+ * I_k = -p_k * log2(p_k + 1e-30) / log2(K), without the upsampled logits or the softmax in memory.  2 <= K <= 32 (log2(1) = 0
+ * is the divisor), sizes > 1.  bwd: dlogits[B,h,w] rows of stride ldl (columns >= K zeroed) = the gradient under dout f32[B,K,H,W]
+ * (contiguous); p is recomputed per output pixel, g_k = p_k * (t_k - sum_j p_j t_j) with t = dout * dI/dp, reduced onto the
+ * low-resolution grid by the two gather passes of onda_upsample_ce_bwd (fixed order, no atomics: two runs give the same bits);
+ * width pairs with onda_upsample_ce_fused(w, W) == 0 go through a per-pixel g[B,K,H,W] in `ws` and the gather of
+ * onda_upsample_bwd instead.  ws: onda_upsample_entropy_bwd_ws floats, for either route. */
+int onda_upsample_entropy_fwd(const float* logits, int ldl, float* out, int B, int h, int w, int K, int H, int W, onda_stream_t s);
+int64_t onda_upsample_entropy_bwd_ws(int B, int w, int K, int H, int W);
+int onda_upsample_entropy_bwd(const float* logits, int ldl, const float* dout, float* dlogits, float* ws, int B, int h, int w, int K,
+                              int H, int W, onda_stream_t s);
 /* fused evaluation tail: upsample -> (softmax) -> argmax class map u8[B,H,W]
  * (adaptation_model.py:145-153) without materialising the upsampled tensor */
 int onda_upsample_argmax(const float* logits, int ldl, uint8_t* cls, int B, int h, int w, int K, int H, int W,

@@ -111,6 +111,9 @@ SIGNATURES = {
     "onda_upsample_ce_fwd": (I, [P, I, P, P, P, I, I, I, I, I, I, P]),
     "onda_upsample_ce_bwd_ws": (L, [I, I, I, I]),
     "onda_upsample_ce_bwd": (I, [P, I, P, P, P, F, P, P, I, I, I, I, I, I, P]),
+    "onda_upsample_entropy_fwd": (I, [P, I, P, I, I, I, I, I, I, P]),
+    "onda_upsample_entropy_bwd_ws": (L, [I, I, I, I, I]),
+    "onda_upsample_entropy_bwd": (I, [P, I, P, P, P, I, I, I, I, I, I, P]),
     "onda_upsample_argmax_hist": (I, [P, I, P, P, P, I, I, I, I, I, I, P]),
     "onda_ece_bins_local": (I, []),
     "onda_upsample_ece": (I, [P, I, P, P, I, I, P, I, I, I, I, I, I, P]),

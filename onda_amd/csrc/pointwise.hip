@@ -1,5 +1,5 @@
 // HBM-bound pointwise / stencil kernels of the hot path: ceil-mode max-pool, the SE gate,
-// channel scaling, align_corners bilinear upsampling (plain, gradient, fused argmax).
+// channel scaling, align_corners bilinear upsampling (plain, gradient, fused argmax / cross-entropy / calibration / entropy map).
 #include "common.h"
 
 namespace {
@@ -678,6 +678,173 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_cols_kernel(const float* 
   }
 }
 
+// ---- ADVENT's entropy map: prob_2_entropy(softmax(interp(logits))) (advent_da.py:94-128, func.py:71-74) ----------------------
+// The discriminators read I_k = -p_k * log2(p_k + 1e-30) / log2(K), p = softmax over the K upsampled logits of a pixel.  Only the
+// map itself has to exist: the upsampled logits and the softmax (159 MB each at 512x1024, batch 4) live in registers, in
+// both directions.  p is exp(v - max) / sum as ATen's softmax; the constants are float32 as the reference's tensors.
+constexpr float ENT_EPS = 1e-30f;
+constexpr float ENT_LN2 = 0.6931471805599453f;
+
+// p[k] = softmax(v)[k] in place over k < K
+__device__ __forceinline__ void ent_softmax(float* v, int K) {
+  float m = -INFINITY, sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < UCE_KMAX; ++k)
+    if (k < K) m = fmaxf(m, v[k]);
+#pragma unroll
+  for (int k = 0; k < UCE_KMAX; ++k)
+    if (k < K) {
+      v[k] = expf(v[k] - m);
+      sum += v[k];
+    }
+#pragma unroll
+  for (int k = 0; k < UCE_KMAX; ++k)
+    if (k < K) v[k] = v[k] / sum;
+}
+
+// t[k] (the map's upstream gradient) -> the gradient with respect to the pixel's K logits, in place:
+// t_k * dI/dp_k, dI/dp = -(log2(p + eps) + p / ((p + eps) ln 2)) / log2 K  (what autograd derives from the expression above),
+// then the softmax Jacobian g_k = p_k * (t_k - sum_j p_j t_j)
+__device__ __forceinline__ void ent_grad(const float* p, float* t, int K, float log2k) {
+  float dot = 0.f;
+#pragma unroll
+  for (int k = 0; k < UCE_KMAX; ++k)
+    if (k < K) {
+      const float q = p[k] + ENT_EPS;
+      t[k] = t[k] * (-(log2f(q) + p[k] / (q * ENT_LN2)) / log2k);
+      dot += p[k] * t[k];
+    }
+#pragma unroll
+  for (int k = 0; k < UCE_KMAX; ++k)
+    if (k < K) t[k] = p[k] * (t[k] - dot);
+}
+
+// One thread per output pixel, consecutive threads along X: the loads of a `dout` plane and the stores of an `out` plane
+// coalesce.  GRAD = false: out = the map.  GRAD = true: out = the per-pixel gradient g[B][K][H][W] with respect to the upsampled
+// logits (the route of the width pairs the two-pass backward below does not take; upsample_bwd_kernel gathers it).
+template <bool GRAD>
+__global__ __launch_bounds__(256) void upsample_entropy_kernel(const float* __restrict__ logits, int ldl,
+                                                               const float* __restrict__ dout, float* __restrict__ out, int B,
+                                                               int h, int w, int K, int H, int W, float sy, float sx,
+                                                               float log2k) {
+  const bool vec = (ldl & 3) == 0 && ((K + 3) & ~3) <= ldl && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;  // = upsample_kernel
+  const size_t total = (size_t)B * H * W, plane = (size_t)H * W;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    const int X = (int)(e % W);
+    const size_t q = e / W;
+    const int Y = (int)(q % H), b = (int)(q / H);
+    const Lerp ly = lerp_index(Y, sy, h), lx = lerp_index(X, sx, w);
+    const float* p00 = logits + (((size_t)b * h + ly.i0) * w + lx.i0) * ldl;
+    const float* p01 = logits + (((size_t)b * h + ly.i0) * w + lx.i1) * ldl;
+    const float* p10 = logits + (((size_t)b * h + ly.i1) * w + lx.i0) * ldl;
+    const float* p11 = logits + (((size_t)b * h + ly.i1) * w + lx.i1) * ldl;
+    float v[UCE_KMAX];
+    if (vec) {
+#pragma unroll
+      for (int k = 0; k < UCE_KMAX; k += 4)
+        if (k < K) {
+          const f32x4 a = LD4(p00 + k), c = LD4(p01 + k), d = LD4(p10 + k), f = LD4(p11 + k);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[k + j] = ly.l0 * (lx.l0 * a[j] + lx.l1 * c[j]) + ly.l1 * (lx.l0 * d[j] + lx.l1 * f[j]);  // = upsample_kernel
+        }
+    } else {
+#pragma unroll
+      for (int k = 0; k < UCE_KMAX; ++k)
+        if (k < K) v[k] = ly.l0 * (lx.l0 * p00[k] + lx.l1 * p01[k]) + ly.l1 * (lx.l0 * p10[k] + lx.l1 * p11[k]);
+    }
+    ent_softmax(v, K);
+    const size_t o = (size_t)b * K * plane + (size_t)Y * W + X;
+    if (GRAD) {
+      float t[UCE_KMAX];
+#pragma unroll
+      for (int k = 0; k < UCE_KMAX; ++k)
+        if (k < K) t[k] = dout[o + k * plane];
+      ent_grad(v, t, K, log2k);
+#pragma unroll
+      for (int k = 0; k < UCE_KMAX; ++k)
+        if (k < K) out[o + k * plane] = t[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < UCE_KMAX; ++k)
+        if (k < K) out[o + k * plane] = -(v[k] * log2f(v[k] + ENT_EPS)) / log2k;
+    }
+  }
+}
+
+// Pass A of the two-pass backward: upsample_ce_bwd_rows_kernel with the pixel's gradient vector taken from `dout` (each
+// thread reads its pixel's K values plane by plane: consecutive threads, consecutive addresses) instead of from a label.
+// Same workgroup shape, same LDS layout and size, same fixed summation order; pass B is upsample_ce_bwd_cols_kernel itself.
+__global__ __launch_bounds__(256) void upsample_entropy_bwd_rows_kernel(const float* __restrict__ logits, int ldl,
+                                                                        const float* __restrict__ dout, float* __restrict__ tmp,
+                                                                        int B, int h, int w, int K, int H, int W, float sy,
+                                                                        float sx, float inv_sx, int CW, float log2k) {
+  extern __shared__ float uce_lds[];
+  float* r = uce_lds;                    // [CW + 2][K]
+  float* g = r + (CW + 2) * K;           // [UCE_SPAN][K]
+  float* lw = g + UCE_SPAN * K;          // [UCE_SPAN]
+  int* li = reinterpret_cast<int*>(lw + UCE_SPAN);  // [UCE_SPAN]
+  const int t = threadIdx.x;
+  const int xb = blockIdx.x * CW, xe = min(w, xb + CW);
+  const int Y = blockIdx.y % H, b = blockIdx.y / H;
+  const Lerp ly = lerp_index(Y, sy, h);
+  int X0 = (int)floorf((float)(xb - 1) * inv_sx) - 1, X1 = (int)ceilf((float)xe * inv_sx) + 1;
+  X0 = max(X0, 0);
+  X1 = min(X1, W - 1);
+  const int span = X1 - X0 + 1;          // <= UCE_SPAN (the host picks CW)
+  const int x_lo = max(xb - 1, 0), nxr = min(w, xe + 1) - x_lo;
+  const float* p0 = logits + ((size_t)b * h + ly.i0) * w * ldl;
+  const float* p1 = logits + ((size_t)b * h + ly.i1) * w * ldl;
+  for (int idx = t; idx < nxr * K; idx += 256) {
+    const int x = idx / K, k = idx - x * K;
+    r[idx] = ly.l0 * p0[(size_t)(x_lo + x) * ldl + k] + ly.l1 * p1[(size_t)(x_lo + x) * ldl + k];
+  }
+  __syncthreads();
+  const size_t plane = (size_t)H * W;
+  const float* drow = dout + (size_t)b * K * plane + (size_t)Y * W;
+  for (int i = t; i < span; i += 256) {
+    const int X = X0 + i;
+    const Lerp lx = lerp_index(X, sx, w);
+    li[i] = lx.i0;
+    lw[i] = lx.i1 != lx.i0 ? lx.l1 : 0.f;
+    float* gi = g + i * K;
+    const bool inside = lx.i0 >= x_lo && lx.i1 < x_lo + nxr;  // (slack pixels outside the block's rows contribute nothing)
+    if (!inside) {
+      for (int k = 0; k < K; ++k) gi[k] = 0.f;
+      continue;
+    }
+    const float* r0 = r + (lx.i0 - x_lo) * K;
+    const float* r1 = r + (lx.i1 - x_lo) * K;
+    float v[UCE_KMAX], u[UCE_KMAX];
+#pragma unroll
+    for (int k = 0; k < UCE_KMAX; ++k)
+      if (k < K) {
+        v[k] = lx.l0 * r0[k] + lx.l1 * r1[k];
+        u[k] = drow[k * plane + X];
+      }
+    ent_softmax(v, K);
+    ent_grad(v, u, K, log2k);
+#pragma unroll
+    for (int k = 0; k < UCE_KMAX; ++k)
+      if (k < K) gi[k] = u[k];
+  }
+  __syncthreads();
+  float* out = tmp + (((size_t)b * H + Y) * w) * K;
+  for (int idx = t; idx < (xe - xb) * K; idx += 256) {
+    const int xr = idx / K, k = idx - xr * K, x = xb + xr;
+    int A0 = (int)floorf((float)(x - 1) * inv_sx) - 1, A1 = (int)ceilf((float)(x + 1) * inv_sx) + 1;
+    A0 = max(A0, X0);
+    A1 = min(A1, X1);
+    float acc = 0.f;
+    for (int X = A0; X <= A1; ++X) {
+      const int i = X - X0, i0 = li[i];
+      const float l1 = lw[i];
+      const float wx = i0 == x ? 1.f - l1 : (i0 + 1 == x ? l1 : 0.f);
+      acc += wx * g[i * K + k];
+    }
+    out[(size_t)x * K + k] = acc;
+  }
+}
+
 static inline unsigned ew_grid(size_t total) {
   size_t g = (total + 255) / 256;
   if (g > 16384) g = 16384;
@@ -851,6 +1018,56 @@ int onda_upsample_ce_bwd(const float* logits, int ldl, const uint8_t* labels, co
   }
   hipLaunchKernelGGL(upsample_ce_bwd_rows_kernel, dim3((w + CW - 1) / CW, B * H), dim3(256), lds, ONDA_STREAM(s), logits, ldl, labels,
                      result, gscale, w_ce, ws, B, h, w, K, H, W, sy, sx, 1.f / sx, CW);
+  hipLaunchKernelGGL(upsample_ce_bwd_cols_kernel, dim3(ew_grid((size_t)B * h * w * ldl)), dim3(256), 0, ONDA_STREAM(s), ws, dlogits,
+                     ldl, B, h, w, K, H, sy, 1.f / sy);
+  return ONDA_LAUNCH_RESULT();
+}
+
+int onda_upsample_entropy_fwd(const float* logits, int ldl, float* out, int B, int h, int w, int K, int H, int W, onda_stream_t s) {
+  ONDA_REQUIRE(logits && out && K >= 2 && K <= ldl && K <= UCE_KMAX && B >= 1 && h > 1 && w > 1 && H > 1 && W > 1);
+  hipLaunchKernelGGL((upsample_entropy_kernel<false>), dim3(ew_grid((size_t)B * H * W)), dim3(256), 0, ONDA_STREAM(s), logits, ldl,
+                     static_cast<const float*>(nullptr), out, B, h, w, K, H, W, ac_scale(h, H), ac_scale(w, W),
+                     (float)log2((double)K));
+  return ONDA_LAUNCH_RESULT();
+}
+
+int64_t onda_upsample_entropy_bwd_ws(int B, int w, int K, int H, int W) {
+  return onda_upsample_ce_fused(w, W) ? (int64_t)B * H * w * K : (int64_t)B * K * H * W;
+}
+
+int onda_upsample_entropy_bwd(const float* logits, int ldl, const float* dout, float* dlogits, float* ws, int B, int h, int w, int K,
+                              int H, int W, onda_stream_t s) {
+  ONDA_REQUIRE(logits && dout && dlogits && ws && K >= 2 && K <= ldl && K <= UCE_KMAX && B >= 1 && h > 1 && w > 1 && H > 1 && W > 1);
+  const float sy = ac_scale(h, H), sx = ac_scale(w, W), log2k = (float)log2((double)K);
+  const int CW = uce_block_cols(w, W);
+  if (CW < 1) {
+    // past what pass A's span takes: per-pixel gradient into ws[B][K][H][W], then the plain upsample gather (which leaves the
+    // padding columns alone: zero the rows first)
+    if (ldl > K) {
+      const hipError_t e = hipMemsetAsync(dlogits, 0, (size_t)B * h * w * ldl * sizeof(float), ONDA_STREAM(s));
+      if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL((upsample_entropy_kernel<true>), dim3(ew_grid((size_t)B * H * W)), dim3(256), 0, ONDA_STREAM(s), logits, ldl,
+                       dout, ws, B, h, w, K, H, W, sy, sx, log2k);
+    hipLaunchKernelGGL(upsample_bwd_kernel, dim3(ew_grid((size_t)B * h * w * K)), dim3(256), 0, ONDA_STREAM(s), ws, dlogits, ldl, B,
+                       h, w, K, H, W, sy, sx, 1.f / sy, 1.f / sx);
+    return ONDA_LAUNCH_RESULT();
+  }
+  // the LDS of upsample_ce_bwd_rows_kernel, byte for byte (the gradient vector comes from `dout` through registers, not
+  // through LDS): 59 KB at 19 classes, 95 KB at UCE_KMAX -- above 64 KB the kernel asks for its size once
+  const size_t lds = ((size_t)(CW + 2) * K + (size_t)UCE_SPAN * K + 2 * UCE_SPAN) * sizeof(float);
+  ONDA_REQUIRE(lds <= 160 * 1024);
+  if (lds > 64 * 1024) {
+    static size_t granted = 0;
+    if (lds > granted) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(upsample_entropy_bwd_rows_kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return (int)e;
+      granted = lds;
+    }
+  }
+  hipLaunchKernelGGL(upsample_entropy_bwd_rows_kernel, dim3((w + CW - 1) / CW, B * H), dim3(256), lds, ONDA_STREAM(s), logits, ldl,
+                     dout, ws, B, h, w, K, H, W, sy, sx, 1.f / sx, CW, log2k);
   hipLaunchKernelGGL(upsample_ce_bwd_cols_kernel, dim3(ew_grid((size_t)B * h * w * ldl)), dim3(256), 0, ONDA_STREAM(s), ws, dlogits,
                      ldl, B, h, w, K, H, sy, 1.f / sy);
   return ONDA_LAUNCH_RESULT();

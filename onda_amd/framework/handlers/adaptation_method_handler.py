@@ -1,11 +1,14 @@
-"""Drop-in for ``framework/handlers/adaptation_method_handler.py`` (:11-40): the prototype methods
-(the ADVENT baselines are out of scope)."""
-ADAPTATION_METHOD_NAMES = ["PROTO_ONLINE", "PROTO_ONLINE_VSWITCH", "PROTO_ONLINE_HSWITCH", "PROTO_ONLINE_HYBRIDSWITCH"]
+"""Drop-in for ``framework/handlers/adaptation_method_handler.py`` (:11-40): the prototype methods and
+the ADVENT baseline (PROTO_ADVENT, the combination of the two, is not mirrored)."""
+ADAPTATION_METHOD_NAMES = ["ADVENT", "PROTO_ONLINE", "PROTO_ONLINE_VSWITCH", "PROTO_ONLINE_HSWITCH", "PROTO_ONLINE_HYBRIDSWITCH"]
 
 
 def get_adapt_method(cfg):
     name = cfg.METHOD.ADAPTATION.NAME
     assert name in ADAPTATION_METHOD_NAMES, f"cfg.METHOD.ADAPTATION.NAME not in {ADAPTATION_METHOD_NAMES}"
+    if name == "ADVENT":
+        from onda_amd.framework.domain_adaptation.methods.advent_da import advent
+        return advent
     if name == "PROTO_ONLINE":
         from onda_amd.framework.domain_adaptation.methods.prototypes import online_proDA
         return online_proDA

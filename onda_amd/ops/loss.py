@@ -1,6 +1,8 @@
 """The segmentation head's tail: class slices, fused CE / RCE / MRKLD (and, off the default path, MRENT and the JS term),
-softmax statistics, bilinear upsampling (+ fused cross-entropy / argmax / confusion matrix), the device-side prior select."""
+softmax statistics, bilinear upsampling (+ fused cross-entropy / argmax / confusion matrix / calibration table / ADVENT's
+entropy map), the device-side prior select."""
 import ctypes
+import math
 import os
 from ctypes import byref
 
@@ -204,6 +206,47 @@ def upsample_ce(out, labels):
     labels = labels.to(device=out.device, dtype=torch.uint8).long()
     up = UpsampleFn.apply(out, tuple(labels.shape[1:]))
     return torch.nn.functional.cross_entropy(up, labels.masked_fill(labels >= K, -100), ignore_index=-100)
+
+
+class UpsampleEntropyFn(torch.autograd.Function):
+    """prob_2_entropy(softmax(interp(out), 1)) -> f32[B,K,H,W] (ADVENT's discriminator input, advent_da.py:94-128): ONE pass in
+    each direction, the upsampled logits and the softmax in registers only (csrc/pointwise.hip).  2 <= K <= 32."""
+
+    @staticmethod
+    def forward(ctx, out, size):
+        rows, ld, _, K = logits_rows(out)
+        B, _, h, w = out.shape
+        H, W = size
+        ent = torch.empty(B, K, H, W, device=out.device, dtype=torch.float32)
+        call("onda_upsample_entropy_fwd", _p(rows), ld, _p(ent), B, h, w, K, H, W, _stream())
+        ctx.save_for_backward(rows)
+        ctx.meta = (ld, B, h, w, K, H, W)
+        ctx.set_materialize_grads(False)
+        return ent
+
+    @staticmethod
+    def backward(ctx, dent):
+        if dent is None:
+            return None, None
+        rows, = ctx.saved_tensors
+        ld, B, h, w, K, H, W = ctx.meta
+        dent = dent.to(torch.float32).contiguous()
+        dl = torch.empty(B, h, w, ld, device=rows.device, dtype=torch.float32)
+        ws = torch.empty(query("onda_upsample_entropy_bwd_ws", B, w, K, H, W), device=rows.device, dtype=torch.float32)
+        call("onda_upsample_entropy_bwd", _p(rows), ld, _p(dent), _p(dl), _p(ws), B, h, w, K, H, W, _stream())
+        return dl[..., :K].permute(0, 3, 1, 2), None
+
+
+def upsample_entropy(out, size):
+    """ADVENT's entropy map of the model's `out` at `size` = (H, W), differentiable with respect to `out`."""
+    return UpsampleEntropyFn.apply(out, tuple(size))
+
+
+def upsample_entropy_composed(out, size):
+    """The same map the way the reference composes it -- UpsampleFn, torch.softmax, the entropy expression, autograd for the
+    backward pass: three [B,K,H,W] tensors in memory.  The yardstick of tools/entropy_timing.py and of the step test."""
+    p = torch.softmax(UpsampleFn.apply(out, tuple(size)), 1)
+    return -torch.mul(p, torch.log2(p + 1e-30)) / math.log2(out.shape[1])
 
 
 def upsample_argmax(out, size):
