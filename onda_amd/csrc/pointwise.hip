@@ -1,6 +1,7 @@
 // HBM-bound pointwise / stencil kernels of the hot path: ceil-mode max-pool, the SE gate,
 // channel scaling, align_corners bilinear upsampling (plain, gradient, fused argmax / cross-entropy / calibration / entropy map).
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -224,10 +225,98 @@ __device__ __forceinline__ Lerp lerp_index(int dst, float scale, int in_size) {
   return o;
 }
 
+// One output pixel of a [B][H][W] grid over rows[B][h][w][ldl]: where it is, the taps of both axes, the four rows it reads
+struct Pixel {
+  int b, Y, X;
+  Lerp ly, lx;
+  const float *p00, *p01, *p10, *p11;
+};
+__device__ __forceinline__ Pixel pixel_at(size_t e, const float* rows, int ldl, int h, int w, int H, int W, float sy, float sx) {
+  Pixel p;
+  p.X = (int)(e % W);
+  const size_t q = e / W;
+  p.Y = (int)(q % H), p.b = (int)(q / H);
+  p.ly = lerp_index(p.Y, sy, h), p.lx = lerp_index(p.X, sx, w);
+  p.p00 = rows + (((size_t)p.b * h + p.ly.i0) * w + p.lx.i0) * ldl;
+  p.p01 = rows + (((size_t)p.b * h + p.ly.i0) * w + p.lx.i1) * ldl;
+  p.p10 = rows + (((size_t)p.b * h + p.ly.i1) * w + p.lx.i0) * ldl;
+  p.p11 = rows + (((size_t)p.b * h + p.ly.i1) * w + p.lx.i1) * ldl;
+  return p;
+}
+
+// rows are ldl floats apart; whole 16-byte groups of classes when the padding allows (the head's rows are 32 floats: 5 loads
+// per corner for 19 classes instead of 19).  A macro on purpose: as a function the three tests are folded into one block
+// before they are inlined and every kernel that asks comes out with other code (docs/experiments.md, 2026-10-18)
+#define ROWS_VEC(rows, ldl, K) (((ldl) & 3) == 0 && (((K) + 3) & ~3) <= (ldl) && (reinterpret_cast<uintptr_t>(rows) & 15) == 0)
+
+// the interpolated value from its four corners (a, c: row i0 of y at columns i0, i1 of x; d, f: row i1): every kernel of the
+// family takes it from here, so all of them round alike
+__device__ __forceinline__ float bilerp(const Lerp& ly, const Lerp& lx, float a, float c, float d, float f) {
+  return ly.l0 * (lx.l0 * a + lx.l1 * c) + ly.l1 * (lx.l0 * d + lx.l1 * f);
+}
+
+// the four classes k .. k + 3 of a pixel into o[0..4) (without `vec`, those >= K: 0, never looked at)
+__device__ __forceinline__ void bilerp4(const Pixel& p, bool vec, int k, int K, float* o) {
+  f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = a, d = a, f = a;
+  if (vec) {
+    a = LD4(p.p00 + k), c = LD4(p.p01 + k), d = LD4(p.p10 + k), f = LD4(p.p11 + k);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (k + j < K) a[j] = p.p00[k + j], c[j] = p.p01[k + j], d[j] = p.p10[k + j], f[j] = p.p11[k + j];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = bilerp(p.ly, p.lx, a[j], c[j], d[j], f[j]);
+}
+
+constexpr int UCE_KMAX = 32;  // classes the kernels that keep a pixel's whole K-vector in registers take
+
+// m = max of v[0..K), v[k] = exp(v[k] - m) in place; returns the sum (ATen's softmax up to the division)
+__device__ __forceinline__ float exp_sum(float* v, int K) {
+  float m = -INFINITY, sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < UCE_KMAX; ++k)
+    if (k < K) m = fmaxf(m, v[k]);
+#pragma unroll
+  for (int k = 0; k < UCE_KMAX; ++k)
+    if (k < K) {
+      v[k] = expf(v[k] - m);
+      sum += v[k];
+    }
+  return sum;
+}
+
 // The confusion matrix (ARGMAX with `hist`) is counted per workgroup in LDS and flushed once: one global atomic per non-empty
 // cell and workgroup instead of one per pixel (K * K counters shared by every pixel of the batch: 4.2 M adds to 361 addresses
 // took 2.1 of the 20.3 ms of an 8-frame evaluation pass).  Integer adds: the result does not depend on the order.
 constexpr int UPS_HIST_LDS = 1024;  // cells a workgroup counts in LDS (K <= 32); larger K: global atomics per pixel
+
+template <class T>
+__device__ __forceinline__ void lds_zero(T* p, int n) {
+  for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0;
+}
+
+// one (ground truth g, prediction arg) pair into the workgroup's LDS counts or straight into `hist`; fast_hist
+// (func.py:77-79): rows = ground truth in [0,K), columns = prediction
+__device__ __forceinline__ void hist_count(unsigned* lh, unsigned long long* hist, bool local, int g, int arg, int K) {
+  if (g < K) {
+    if (local) atomicAdd(lh + g * K + arg, 1u);
+    else atomicAdd(&hist[g * K + arg], 1ull);
+  }
+}
+
+// global[0..n) += lds_counts[0..n), after a barrier.  Every workgroup starts its flush at a different cell: the adds of one
+// moment go to different addresses
+__device__ __forceinline__ void flush_rotated(const unsigned* lds_counts, unsigned long long* global, unsigned n) {
+  const unsigned start = (blockIdx.x * 37u) % n;
+  for (unsigned i = threadIdx.x; i < n; i += blockDim.x) {
+    unsigned cell = i + start;
+    if (cell >= n) cell -= n;
+    const unsigned long long c = lds_counts[cell];
+    if (c) atomicAdd(&global[cell], c);
+  }
+}
+
 template <bool ARGMAX>
 __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__ logits, int ldl,
                                                        float* __restrict__ out, uint8_t* __restrict__ cls,
@@ -237,22 +326,13 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
   const int KK = K * K;
   const bool local = ARGMAX && hist != nullptr && KK <= UPS_HIST_LDS;
   if (local) {
-    for (int i = threadIdx.x; i < KK; i += blockDim.x) lh[i] = 0u;
+    lds_zero(lh, KK);
     __syncthreads();
   }
-  // rows of `logits` are ldl floats apart; whole 16-byte groups of classes when the padding allows (the head's rows are
-  // 32 floats: 5 loads per corner for 19 classes instead of 19)
-  const bool vec = (ldl & 3) == 0 && ((K + 3) & ~3) <= ldl && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
+  const bool vec = ROWS_VEC(logits, ldl, K);
   const size_t total = (size_t)B * H * W;
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const int X = (int)(e % W);
-    const size_t q = e / W;
-    const int Y = (int)(q % H), b = (int)(q / H);
-    const Lerp ly = lerp_index(Y, sy, h), lx = lerp_index(X, sx, w);
-    const float* p00 = logits + (((size_t)b * h + ly.i0) * w + lx.i0) * ldl;
-    const float* p01 = logits + (((size_t)b * h + ly.i0) * w + lx.i1) * ldl;
-    const float* p10 = logits + (((size_t)b * h + ly.i1) * w + lx.i0) * ldl;
-    const float* p11 = logits + (((size_t)b * h + ly.i1) * w + lx.i1) * ldl;
+    const Pixel p = pixel_at(e, logits, ldl, h, w, H, W, sy, sx);
     float best = -INFINITY;
     int arg = 0;
     auto take = [&](int k, float v) {
@@ -262,40 +342,27 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
           arg = k;
         }
       } else {
-        out[(((size_t)b * K + k) * H + Y) * W + X] = v;
+        out[(((size_t)p.b * K + k) * H + p.Y) * W + p.X] = v;
       }
     };
     if (vec) {
       for (int k = 0; k < K; k += 4) {
-        const f32x4 a = LD4(p00 + k), c = LD4(p01 + k), d = LD4(p10 + k), f = LD4(p11 + k);
+        const f32x4 a = LD4(p.p00 + k), c = LD4(p.p01 + k), d = LD4(p.p10 + k), f = LD4(p.p11 + k);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (k + j < K) take(k + j, ly.l0 * (lx.l0 * a[j] + lx.l1 * c[j]) + ly.l1 * (lx.l0 * d[j] + lx.l1 * f[j]));
+          if (k + j < K) take(k + j, bilerp(p.ly, p.lx, a[j], c[j], d[j], f[j]));
       }
     } else {
-      for (int k = 0; k < K; ++k) take(k, ly.l0 * (lx.l0 * p00[k] + lx.l1 * p01[k]) + ly.l1 * (lx.l0 * p10[k] + lx.l1 * p11[k]));
+      for (int k = 0; k < K; ++k) take(k, bilerp(p.ly, p.lx, p.p00[k], p.p01[k], p.p10[k], p.p11[k]));
     }
     if (ARGMAX) {
       if (cls) cls[e] = (uint8_t)arg;
-      if (hist) {  // fast_hist (func.py:77-79): rows = ground truth in [0,K), columns = prediction
-        const int g = gt[e];
-        if (g < K) {
-          if (local) atomicAdd(&lh[g * K + arg], 1u);
-          else atomicAdd(&hist[g * K + arg], 1ull);
-        }
-      }
+      if (hist) hist_count(lh, hist, local, gt[e], arg, K);
     }
   }
   if (local) {
     __syncthreads();
-    // every workgroup starts its flush at a different cell: the adds of one moment go to different addresses
-    const int start = (int)((blockIdx.x * 37u) % (unsigned)KK);
-    for (int i = threadIdx.x; i < KK; i += blockDim.x) {
-      int cell = i + start;
-      if (cell >= KK) cell -= KK;
-      const unsigned n = lh[cell];
-      if (n) atomicAdd(&hist[cell], (unsigned long long)n);
-    }
+    flush_rotated(lh, hist, KK);
   }
 }
 
@@ -341,43 +408,21 @@ __global__ __launch_bounds__(256) void upsample_ece_kernel(const float* __restri
   unsigned long long* lsum = ece_lds;
   unsigned long long* lcnt = ece_lds + R;
   const bool hlocal = hist != nullptr && KK <= UPS_HIST_LDS;
-  if (local)
-    for (int i = threadIdx.x; i < 2 * R; i += blockDim.x) ece_lds[i] = 0ull;
-  if (hlocal)
-    for (int i = threadIdx.x; i < KK; i += blockDim.x) lh[i] = 0u;
+  if (local) lds_zero(ece_lds, 2 * R);
+  if (hlocal) lds_zero(lh, KK);
   __syncthreads();
-  const bool vec = (ldl & 3) == 0 && ((K + 3) & ~3) <= ldl && (reinterpret_cast<uintptr_t>(rows) & 15) == 0;
+  const bool vec = ROWS_VEC(rows, ldl, K);
   const size_t total = (size_t)B * H * W;
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
     int arg = 0;
-    const int X = (int)(e % W);
-    const size_t q = e / W;
-    const int Y = (int)(q % H), b = (int)(q / H);
-    const Lerp ly = lerp_index(Y, sy, h), lx = lerp_index(X, sx, w);
-    const float* p00 = rows + (((size_t)b * h + ly.i0) * w + lx.i0) * ldl;
-    const float* p01 = rows + (((size_t)b * h + ly.i0) * w + lx.i1) * ldl;
-    const float* p10 = rows + (((size_t)b * h + ly.i1) * w + lx.i0) * ldl;
-    const float* p11 = rows + (((size_t)b * h + ly.i1) * w + lx.i1) * ldl;
-    // the four classes k .. k + 3 (those >= K: 0, never looked at)
-    auto group = [&](int k, float* o) {
-      f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = a, d = a, f = a;
-      if (vec) {
-        a = LD4(p00 + k), c = LD4(p01 + k), d = LD4(p10 + k), f = LD4(p11 + k);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (k + j < K) a[j] = p00[k + j], c[j] = p01[k + j], d[j] = p10[k + j], f[j] = p11[k + j];
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = ly.l0 * (lx.l0 * a[j] + lx.l1 * c[j]) + ly.l1 * (lx.l0 * d[j] + lx.l1 * f[j]);  // = upsample_kernel
-    };
+    const Pixel p = pixel_at(e, rows, ldl, h, w, H, W, sy, sx);
     float best = -INFINITY, v[KREG ? ECE_KREG : 4];
     bool bad = false;
     if (KREG) {
 #pragma unroll
       for (int k = 0; k < ECE_KREG; k += 4)
         if (k < K) {
-          group(k, v + k);
+          bilerp4(p, vec, k, K, v + k);
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             if (k + j < K) {
@@ -387,7 +432,7 @@ __global__ __launch_bounds__(256) void upsample_ece_kernel(const float* __restri
         }
     } else {
       for (int k = 0; k < K; k += 4) {
-        group(k, v);
+        bilerp4(p, vec, k, K, v);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           if (k + j < K) {
@@ -405,7 +450,7 @@ __global__ __launch_bounds__(256) void upsample_ece_kernel(const float* __restri
           if (k < K) sum += expf(v[k] - best);
       } else {
         for (int k = 0; k < K; k += 4) {
-          group(k, v);
+          bilerp4(p, vec, k, K, v);
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             if (k + j < K) sum += expf(v[j] - best);
@@ -425,14 +470,11 @@ __global__ __launch_bounds__(256) void upsample_ece_kernel(const float* __restri
       if (hit) atomicAdd(&table[(size_t)row * 3 + 1], 1ull);
       atomicAdd(&table[(size_t)row * 3 + 2], 1ull);
     }
-    if (hist && g < K) {  // = upsample_kernel
-      if (hlocal) atomicAdd(&lh[g * K + arg], 1u);
-      else atomicAdd(&hist[g * K + arg], 1ull);
-    }
+    if (hist) hist_count(lh, hist, hlocal, g, arg, K);
   }
   __syncthreads();
   if (local) {
-    // every workgroup starts its flush at a different row, as the confusion matrix below
+    // rotated like the confusion matrix's flush; a row unpacks into its three table columns, so the loop is its own
     const int start = (int)((blockIdx.x * 37u) % (unsigned)R);
     for (int i = threadIdx.x; i < R; i += blockDim.x) {
       int r = i + start;
@@ -446,15 +488,7 @@ __global__ __launch_bounds__(256) void upsample_ece_kernel(const float* __restri
       }
     }
   }
-  if (hlocal) {
-    const int start = (int)((blockIdx.x * 37u) % (unsigned)KK);
-    for (int i = threadIdx.x; i < KK; i += blockDim.x) {
-      int cell = i + start;
-      if (cell >= KK) cell -= KK;
-      const unsigned n = lh[cell];
-      if (n) atomicAdd(&hist[cell], (unsigned long long)n);
-    }
-  }
+  if (hlocal) flush_rotated(lh, hist, KK);
 }
 
 __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restrict__ dout, float* __restrict__ dl,
@@ -497,7 +531,6 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restri
 // batch 4) only to reduce them to one scalar, and its backward pass writes and re-reads a gradient of the same size.  Here
 // every output pixel's K logits are interpolated in registers from the low-resolution rows (4.3 MB: cache-resident) in both
 // directions; only the labels (1 byte per pixel) are streamed.
-constexpr int UCE_KMAX = 32;
 
 // one thread per output pixel: -log softmax(v)[label] for valid labels; per-block partial (sum, count) into ws[block][2]
 __global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(const float* __restrict__ logits, int ldl,
@@ -509,19 +542,12 @@ __global__ __launch_bounds__(256) void upsample_ce_fwd_kernel(const float* __res
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
     const int tl = labels[e];
     if (tl >= K) continue;  // 255 = ignore (loss.py:22-31)
-    const int X = (int)(e % W);
-    const size_t q = e / W;
-    const int Y = (int)(q % H), b = (int)(q / H);
-    const Lerp ly = lerp_index(Y, sy, h), lx = lerp_index(X, sx, w);
-    const float* p00 = logits + (((size_t)b * h + ly.i0) * w + lx.i0) * ldl;
-    const float* p01 = logits + (((size_t)b * h + ly.i0) * w + lx.i1) * ldl;
-    const float* p10 = logits + (((size_t)b * h + ly.i1) * w + lx.i0) * ldl;
-    const float* p11 = logits + (((size_t)b * h + ly.i1) * w + lx.i1) * ldl;
+    const Pixel p = pixel_at(e, logits, ldl, h, w, H, W, sy, sx);
     float v[UCE_KMAX], m = -INFINITY, vt = 0.f;
 #pragma unroll
     for (int k = 0; k < UCE_KMAX; ++k)
       if (k < K) {
-        v[k] = ly.l0 * (lx.l0 * p00[k] + lx.l1 * p01[k]) + ly.l1 * (lx.l0 * p10[k] + lx.l1 * p11[k]);  // = upsample_kernel
+        v[k] = bilerp(p.ly, p.lx, p.p00[k], p.p01[k], p.p10[k], p.p11[k]);
         m = fmaxf(m, v[k]);
         if (k == tl) vt = v[k];
       }
@@ -563,8 +589,83 @@ __global__ __launch_bounds__(256) void upsample_ce_finalize_kernel(const float* 
   }
 }
 
+// ---- ADVENT's entropy map: prob_2_entropy(softmax(interp(logits))) (advent_da.py:94-128, func.py:71-74) ----------------------
+// The discriminators read I_k = -p_k * log2(p_k + 1e-30) / log2(K), p = softmax over the K upsampled logits of a pixel.  Only the
+// map itself has to exist: the upsampled logits and the softmax (159 MB each at 512x1024, batch 4) live in registers, in
+// both directions.  p is exp(v - max) / sum as ATen's softmax; the constants are float32 as the reference's tensors.
+constexpr float ENT_EPS = 1e-30f;
+constexpr float ENT_LN2 = 0.6931471805599453f;
+
+// p[k] = softmax(v)[k] in place over k < K
+__device__ __forceinline__ void ent_softmax(float* v, int K) {
+  const float sum = exp_sum(v, K);
+#pragma unroll
+  for (int k = 0; k < UCE_KMAX; ++k)
+    if (k < K) v[k] = v[k] / sum;
+}
+
+// t[k] (the map's upstream gradient) -> the gradient with respect to the pixel's K logits, in place:
+// t_k * dI/dp_k, dI/dp = -(log2(p + eps) + p / ((p + eps) ln 2)) / log2 K  (what autograd derives from the expression above),
+// then the softmax Jacobian g_k = p_k * (t_k - sum_j p_j t_j)
+__device__ __forceinline__ void ent_grad(const float* p, float* t, int K, float log2k) {
+  float dot = 0.f;
+#pragma unroll
+  for (int k = 0; k < UCE_KMAX; ++k)
+    if (k < K) {
+      const float q = p[k] + ENT_EPS;
+      t[k] = t[k] * (-(log2f(q) + p[k] / (q * ENT_LN2)) / log2k);
+      dot += p[k] * t[k];
+    }
+#pragma unroll
+  for (int k = 0; k < UCE_KMAX; ++k)
+    if (k < K) t[k] = p[k] * (t[k] - dot);
+}
+
+// One thread per output pixel, consecutive threads along X: the loads of a `dout` plane and the stores of an `out` plane
+// coalesce.  GRAD = false: out = the map.  GRAD = true: out = the per-pixel gradient g[B][K][H][W] with respect to the upsampled
+// logits (the route of the width pairs the two-pass backward below does not take; upsample_bwd_kernel gathers it).
+template <bool GRAD>
+__global__ __launch_bounds__(256) void upsample_entropy_kernel(const float* __restrict__ logits, int ldl,
+                                                               const float* __restrict__ dout, float* __restrict__ out, int B,
+                                                               int h, int w, int K, int H, int W, float sy, float sx,
+                                                               float log2k) {
+  const bool vec = ROWS_VEC(logits, ldl, K);
+  const size_t total = (size_t)B * H * W, plane = (size_t)H * W;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    const Pixel p = pixel_at(e, logits, ldl, h, w, H, W, sy, sx);
+    float v[UCE_KMAX];
+    if (vec) {
+#pragma unroll
+      for (int k = 0; k < UCE_KMAX; k += 4)
+        if (k < K) bilerp4(p, true, k, K, &v[k]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < UCE_KMAX; ++k)
+        if (k < K) v[k] = bilerp(p.ly, p.lx, p.p00[k], p.p01[k], p.p10[k], p.p11[k]);
+    }
+    ent_softmax(v, K);
+    const size_t o = (size_t)p.b * K * plane + (size_t)p.Y * W + p.X;
+    if (GRAD) {
+      float t[UCE_KMAX];
+#pragma unroll
+      for (int k = 0; k < UCE_KMAX; ++k)
+        if (k < K) t[k] = dout[o + k * plane];
+      ent_grad(v, t, K, log2k);
+#pragma unroll
+      for (int k = 0; k < UCE_KMAX; ++k)
+        if (k < K) out[o + k * plane] = t[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < UCE_KMAX; ++k)
+        if (k < K) out[o + k * plane] = -(v[k] * log2f(v[k] + ENT_EPS)) / log2k;
+    }
+  }
+}
+
+// ---- the two-pass backward of the fused heads -----------------------------------------------------------------------------
 // Gradient with respect to the LOW-resolution logits.  The interpolation weights are separable, so
-//     dl[y][x][k] = sum_Y wy(Y, y) * ( sum_X wx(X, x) * g[Y][X][k] ),   g = a * (softmax(v) - onehot) at the kept pixels,
+//     dl[y][x][k] = sum_Y wy(Y, y) * ( sum_X wx(X, x) * g[Y][X][k] ),   g = the head's gradient with respect to a pixel's
+//     upsampled logits (cross-entropy: a * (softmax(v) - onehot) at the kept pixels; entropy map: ent_grad of its cotangent),
 // is taken in two gather passes (fixed summation order: deterministic), each output pixel's softmax evaluated about once:
 //   pass A, one workgroup per (image, output row Y, block of CW low-resolution columns): the row's interpolated low-res
 //     rows r[x][k] = ly.l0 * p[y0][x][k] + ly.l1 * p[y1][x][k] go to LDS once, every output pixel of the block's span then
@@ -573,12 +674,28 @@ __global__ __launch_bounds__(256) void upsample_ce_finalize_kernel(const float* 
 //   pass B, one thread per (b, y, x, k): gathers t over its ~2 H/h rows -> dl.
 constexpr int UCE_SPAN = 640;  // output pixels of one pass-A workgroup (LDS: UCE_SPAN * K floats of g)
 
-__global__ __launch_bounds__(256) void upsample_ce_bwd_rows_kernel(const float* __restrict__ logits, int ldl,
-                                                                   const uint8_t* __restrict__ labels,
-                                                                   const float* __restrict__ result,
-                                                                   const float* __restrict__ gscale, float w_ce,
-                                                                   float* __restrict__ tmp, int B, int h, int w, int K, int H, int W,
-                                                                   float sy, float sx, float inv_sx, int CW) {
+// What a head contributes to pass A (`Grad`): which pixels have a gradient, and how a pixel's interpolated logits v[0..K) become
+// its gradient vector gi[0..K).  The structs carry the head's arguments; the two bodies stand in the kernel itself, under
+// `if constexpr`: as member functions they are optimised on their own before they are inlined, and the K-vectors then leave
+// the registers (496 VGPRs and 1.5 KB of scratch for the cross-entropy; docs/experiments.md, 2026-10-18).
+// CeGrad: the cross-entropy of upsample_ce_fwd_kernel (result[1]: its kept pixels) times the upstream gradient *gscale
+// (nullptr: 1) and w_ce.  EntGrad: the entropy map under the cotangent dout[B][K][H][W] (each thread reads its pixel's K values
+// plane by plane: consecutive threads, consecutive addresses).
+struct CeGrad {
+  const uint8_t* labels;
+  const float *result, *gscale;
+  float w_ce;
+};
+struct EntGrad {
+  const float* dout;
+  float log2k;
+};
+
+template <class Grad>
+__global__ __launch_bounds__(256) void upsample_bwd_rows_kernel(const Grad grad, const float* __restrict__ logits, int ldl,
+                                                                float* __restrict__ tmp, int B, int h, int w, int K, int H, int W,
+                                                                float sy, float sx, float inv_sx, int CW) {
+  constexpr bool CE = std::is_same<Grad, CeGrad>::value;
   extern __shared__ float uce_lds[];
   float* r = uce_lds;                    // [CW + 2][K]
   float* g = r + (CW + 2) * K;           // [UCE_SPAN][K]
@@ -587,8 +704,11 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_rows_kernel(const float* 
   const int t = threadIdx.x;
   const int xb = blockIdx.x * CW, xe = min(w, xb + CW);  // low-resolution columns of this workgroup
   const int Y = blockIdx.y % H, b = blockIdx.y / H;
-  const float nvalid = result[1];
-  const float a_ce = nvalid > 0.f ? (gscale ? gscale[0] : 1.f) * w_ce / nvalid : 0.f;
+  float a_ce = 0.f;  // cross-entropy: upstream * w_ce / number of kept pixels (none kept: 0, the gradient is zeros)
+  if constexpr (CE) {
+    const float nvalid = grad.result[1];
+    a_ce = nvalid > 0.f ? (grad.gscale ? grad.gscale[0] : 1.f) * grad.w_ce / nvalid : 0.f;
+  }
   const Lerp ly = lerp_index(Y, sy, h);
   // output columns that read a column of [xb, xe): source coordinate in (xb - 1, xe), with one of slack on either side
   int X0 = (int)floorf((float)(xb - 1) * inv_sx) - 1, X1 = (int)ceilf((float)xe * inv_sx) + 1;
@@ -603,38 +723,61 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_rows_kernel(const float* 
     r[idx] = ly.l0 * p0[(size_t)(x_lo + x) * ldl + k] + ly.l1 * p1[(size_t)(x_lo + x) * ldl + k];
   }
   __syncthreads();
+  const size_t plane = (size_t)H * W;
   for (int i = t; i < span; i += 256) {
     const int X = X0 + i;
     const Lerp lx = lerp_index(X, sx, w);
     li[i] = lx.i0;
     lw[i] = lx.i1 != lx.i0 ? lx.l1 : 0.f;
     float* gi = g + i * K;
-    const int tl = labels[((size_t)b * H + Y) * W + X];
-    const bool inside = lx.i0 >= x_lo && lx.i1 < x_lo + nxr;  // (slack pixels outside the block's rows contribute nothing)
-    if (tl >= K || !inside) {
+    int tl = 0;
+    bool kept = lx.i0 >= x_lo && lx.i1 < x_lo + nxr;  // (slack pixels outside the block's rows contribute nothing)
+    if constexpr (CE) {
+      tl = grad.labels[((size_t)b * H + Y) * W + X];
+      kept = kept && tl < K;
+    }
+    if (!kept) {
       for (int k = 0; k < K; ++k) gi[k] = 0.f;
       continue;
     }
     const float* r0 = r + (lx.i0 - x_lo) * K;
     const float* r1 = r + (lx.i1 - x_lo) * K;
-    float v[UCE_KMAX], m = -INFINITY;
+    float v[UCE_KMAX];
+    if constexpr (CE) {
+      // the maximum comes out of the interpolation loop, not from exp_sum: the label test above tells the compiler K > 0, and
+      // with the loops apart it then keeps v[] as one 32-wide vector (496 VGPRs, scratch)
+      float m = -INFINITY, sum = 0.f;
 #pragma unroll
-    for (int k = 0; k < UCE_KMAX; ++k)
-      if (k < K) {
-        v[k] = lx.l0 * r0[k] + lx.l1 * r1[k];
-        m = fmaxf(m, v[k]);
-      }
-    float sum = 0.f;
+      for (int k = 0; k < UCE_KMAX; ++k)
+        if (k < K) {
+          v[k] = lx.l0 * r0[k] + lx.l1 * r1[k];
+          m = fmaxf(m, v[k]);
+        }
 #pragma unroll
-    for (int k = 0; k < UCE_KMAX; ++k)
-      if (k < K) {
-        v[k] = expf(v[k] - m);
-        sum += v[k];
-      }
-    const float inv = a_ce / sum;
+      for (int k = 0; k < UCE_KMAX; ++k)
+        if (k < K) {
+          v[k] = expf(v[k] - m);
+          sum += v[k];
+        }
+      const float inv = a_ce / sum;
 #pragma unroll
-    for (int k = 0; k < UCE_KMAX; ++k)
-      if (k < K) gi[k] = v[k] * inv - (k == tl ? a_ce : 0.f);
+      for (int k = 0; k < UCE_KMAX; ++k)
+        if (k < K) gi[k] = v[k] * inv - (k == tl ? a_ce : 0.f);
+    } else {
+      const float* drow = grad.dout + (size_t)b * K * plane + (size_t)Y * W;
+      float u[UCE_KMAX];
+#pragma unroll
+      for (int k = 0; k < UCE_KMAX; ++k)
+        if (k < K) {
+          v[k] = lx.l0 * r0[k] + lx.l1 * r1[k];
+          u[k] = drow[k * plane + X];
+        }
+      ent_softmax(v, K);
+      ent_grad(v, u, K, grad.log2k);
+#pragma unroll
+      for (int k = 0; k < UCE_KMAX; ++k)
+        if (k < K) gi[k] = u[k];
+    }
   }
   __syncthreads();
   float* out = tmp + (((size_t)b * H + Y) * w) * K;
@@ -678,173 +821,6 @@ __global__ __launch_bounds__(256) void upsample_ce_bwd_cols_kernel(const float* 
   }
 }
 
-// ---- ADVENT's entropy map: prob_2_entropy(softmax(interp(logits))) (advent_da.py:94-128, func.py:71-74) ----------------------
-// The discriminators read I_k = -p_k * log2(p_k + 1e-30) / log2(K), p = softmax over the K upsampled logits of a pixel.  Only the
-// map itself has to exist: the upsampled logits and the softmax (159 MB each at 512x1024, batch 4) live in registers, in
-// both directions.  p is exp(v - max) / sum as ATen's softmax; the constants are float32 as the reference's tensors.
-constexpr float ENT_EPS = 1e-30f;
-constexpr float ENT_LN2 = 0.6931471805599453f;
-
-// p[k] = softmax(v)[k] in place over k < K
-__device__ __forceinline__ void ent_softmax(float* v, int K) {
-  float m = -INFINITY, sum = 0.f;
-#pragma unroll
-  for (int k = 0; k < UCE_KMAX; ++k)
-    if (k < K) m = fmaxf(m, v[k]);
-#pragma unroll
-  for (int k = 0; k < UCE_KMAX; ++k)
-    if (k < K) {
-      v[k] = expf(v[k] - m);
-      sum += v[k];
-    }
-#pragma unroll
-  for (int k = 0; k < UCE_KMAX; ++k)
-    if (k < K) v[k] = v[k] / sum;
-}
-
-// t[k] (the map's upstream gradient) -> the gradient with respect to the pixel's K logits, in place:
-// t_k * dI/dp_k, dI/dp = -(log2(p + eps) + p / ((p + eps) ln 2)) / log2 K  (what autograd derives from the expression above),
-// then the softmax Jacobian g_k = p_k * (t_k - sum_j p_j t_j)
-__device__ __forceinline__ void ent_grad(const float* p, float* t, int K, float log2k) {
-  float dot = 0.f;
-#pragma unroll
-  for (int k = 0; k < UCE_KMAX; ++k)
-    if (k < K) {
-      const float q = p[k] + ENT_EPS;
-      t[k] = t[k] * (-(log2f(q) + p[k] / (q * ENT_LN2)) / log2k);
-      dot += p[k] * t[k];
-    }
-#pragma unroll
-  for (int k = 0; k < UCE_KMAX; ++k)
-    if (k < K) t[k] = p[k] * (t[k] - dot);
-}
-
-// One thread per output pixel, consecutive threads along X: the loads of a `dout` plane and the stores of an `out` plane
-// coalesce.  GRAD = false: out = the map.  GRAD = true: out = the per-pixel gradient g[B][K][H][W] with respect to the upsampled
-// logits (the route of the width pairs the two-pass backward below does not take; upsample_bwd_kernel gathers it).
-template <bool GRAD>
-__global__ __launch_bounds__(256) void upsample_entropy_kernel(const float* __restrict__ logits, int ldl,
-                                                               const float* __restrict__ dout, float* __restrict__ out, int B,
-                                                               int h, int w, int K, int H, int W, float sy, float sx,
-                                                               float log2k) {
-  const bool vec = (ldl & 3) == 0 && ((K + 3) & ~3) <= ldl && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;  // = upsample_kernel
-  const size_t total = (size_t)B * H * W, plane = (size_t)H * W;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const int X = (int)(e % W);
-    const size_t q = e / W;
-    const int Y = (int)(q % H), b = (int)(q / H);
-    const Lerp ly = lerp_index(Y, sy, h), lx = lerp_index(X, sx, w);
-    const float* p00 = logits + (((size_t)b * h + ly.i0) * w + lx.i0) * ldl;
-    const float* p01 = logits + (((size_t)b * h + ly.i0) * w + lx.i1) * ldl;
-    const float* p10 = logits + (((size_t)b * h + ly.i1) * w + lx.i0) * ldl;
-    const float* p11 = logits + (((size_t)b * h + ly.i1) * w + lx.i1) * ldl;
-    float v[UCE_KMAX];
-    if (vec) {
-#pragma unroll
-      for (int k = 0; k < UCE_KMAX; k += 4)
-        if (k < K) {
-          const f32x4 a = LD4(p00 + k), c = LD4(p01 + k), d = LD4(p10 + k), f = LD4(p11 + k);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[k + j] = ly.l0 * (lx.l0 * a[j] + lx.l1 * c[j]) + ly.l1 * (lx.l0 * d[j] + lx.l1 * f[j]);  // = upsample_kernel
-        }
-    } else {
-#pragma unroll
-      for (int k = 0; k < UCE_KMAX; ++k)
-        if (k < K) v[k] = ly.l0 * (lx.l0 * p00[k] + lx.l1 * p01[k]) + ly.l1 * (lx.l0 * p10[k] + lx.l1 * p11[k]);
-    }
-    ent_softmax(v, K);
-    const size_t o = (size_t)b * K * plane + (size_t)Y * W + X;
-    if (GRAD) {
-      float t[UCE_KMAX];
-#pragma unroll
-      for (int k = 0; k < UCE_KMAX; ++k)
-        if (k < K) t[k] = dout[o + k * plane];
-      ent_grad(v, t, K, log2k);
-#pragma unroll
-      for (int k = 0; k < UCE_KMAX; ++k)
-        if (k < K) out[o + k * plane] = t[k];
-    } else {
-#pragma unroll
-      for (int k = 0; k < UCE_KMAX; ++k)
-        if (k < K) out[o + k * plane] = -(v[k] * log2f(v[k] + ENT_EPS)) / log2k;
-    }
-  }
-}
-
-// Pass A of the two-pass backward: upsample_ce_bwd_rows_kernel with the pixel's gradient vector taken from `dout` (each
-// thread reads its pixel's K values plane by plane: consecutive threads, consecutive addresses) instead of from a label.
-// Same workgroup shape, same LDS layout and size, same fixed summation order; pass B is upsample_ce_bwd_cols_kernel itself.
-__global__ __launch_bounds__(256) void upsample_entropy_bwd_rows_kernel(const float* __restrict__ logits, int ldl,
-                                                                        const float* __restrict__ dout, float* __restrict__ tmp,
-                                                                        int B, int h, int w, int K, int H, int W, float sy,
-                                                                        float sx, float inv_sx, int CW, float log2k) {
-  extern __shared__ float uce_lds[];
-  float* r = uce_lds;                    // [CW + 2][K]
-  float* g = r + (CW + 2) * K;           // [UCE_SPAN][K]
-  float* lw = g + UCE_SPAN * K;          // [UCE_SPAN]
-  int* li = reinterpret_cast<int*>(lw + UCE_SPAN);  // [UCE_SPAN]
-  const int t = threadIdx.x;
-  const int xb = blockIdx.x * CW, xe = min(w, xb + CW);
-  const int Y = blockIdx.y % H, b = blockIdx.y / H;
-  const Lerp ly = lerp_index(Y, sy, h);
-  int X0 = (int)floorf((float)(xb - 1) * inv_sx) - 1, X1 = (int)ceilf((float)xe * inv_sx) + 1;
-  X0 = max(X0, 0);
-  X1 = min(X1, W - 1);
-  const int span = X1 - X0 + 1;          // <= UCE_SPAN (the host picks CW)
-  const int x_lo = max(xb - 1, 0), nxr = min(w, xe + 1) - x_lo;
-  const float* p0 = logits + ((size_t)b * h + ly.i0) * w * ldl;
-  const float* p1 = logits + ((size_t)b * h + ly.i1) * w * ldl;
-  for (int idx = t; idx < nxr * K; idx += 256) {
-    const int x = idx / K, k = idx - x * K;
-    r[idx] = ly.l0 * p0[(size_t)(x_lo + x) * ldl + k] + ly.l1 * p1[(size_t)(x_lo + x) * ldl + k];
-  }
-  __syncthreads();
-  const size_t plane = (size_t)H * W;
-  const float* drow = dout + (size_t)b * K * plane + (size_t)Y * W;
-  for (int i = t; i < span; i += 256) {
-    const int X = X0 + i;
-    const Lerp lx = lerp_index(X, sx, w);
-    li[i] = lx.i0;
-    lw[i] = lx.i1 != lx.i0 ? lx.l1 : 0.f;
-    float* gi = g + i * K;
-    const bool inside = lx.i0 >= x_lo && lx.i1 < x_lo + nxr;  // (slack pixels outside the block's rows contribute nothing)
-    if (!inside) {
-      for (int k = 0; k < K; ++k) gi[k] = 0.f;
-      continue;
-    }
-    const float* r0 = r + (lx.i0 - x_lo) * K;
-    const float* r1 = r + (lx.i1 - x_lo) * K;
-    float v[UCE_KMAX], u[UCE_KMAX];
-#pragma unroll
-    for (int k = 0; k < UCE_KMAX; ++k)
-      if (k < K) {
-        v[k] = lx.l0 * r0[k] + lx.l1 * r1[k];
-        u[k] = drow[k * plane + X];
-      }
-    ent_softmax(v, K);
-    ent_grad(v, u, K, log2k);
-#pragma unroll
-    for (int k = 0; k < UCE_KMAX; ++k)
-      if (k < K) gi[k] = u[k];
-  }
-  __syncthreads();
-  float* out = tmp + (((size_t)b * H + Y) * w) * K;
-  for (int idx = t; idx < (xe - xb) * K; idx += 256) {
-    const int xr = idx / K, k = idx - xr * K, x = xb + xr;
-    int A0 = (int)floorf((float)(x - 1) * inv_sx) - 1, A1 = (int)ceilf((float)(x + 1) * inv_sx) + 1;
-    A0 = max(A0, X0);
-    A1 = min(A1, X1);
-    float acc = 0.f;
-    for (int X = A0; X <= A1; ++X) {
-      const int i = X - X0, i0 = li[i];
-      const float l1 = lw[i];
-      const float wx = i0 == x ? 1.f - l1 : (i0 + 1 == x ? l1 : 0.f);
-      acc += wx * g[i * K + k];
-    }
-    out[(size_t)x * K + k] = acc;
-  }
-}
-
 static inline unsigned ew_grid(size_t total) {
   size_t g = (total + 255) / 256;
   if (g > 16384) g = 16384;
@@ -860,6 +836,34 @@ static inline float ac_scale(int in, int out) { return out > 1 ? (float)(in - 1)
 static inline int uce_block_cols(int w, int W) {
   int CW = (int)((UCE_SPAN - 6) * ac_scale(w, W)) - 2;
   return CW > 64 ? 64 : CW;
+}
+
+// Both passes of a fused head's backward: pass A with the head's `Grad`, then upsample_ce_bwd_cols_kernel.  ws holds
+// B * H * w * K floats.
+template <class Grad>
+int upsample_bwd_two_pass(const Grad& grad, const float* logits, int ldl, float* dlogits, float* ws, int B, int h, int w, int K,
+                          int H, int W, onda_stream_t s) {
+  const float sy = ac_scale(h, H), sx = ac_scale(w, W);
+  const int CW = uce_block_cols(w, W);
+  ONDA_REQUIRE(CW >= 1);
+  const size_t lds = ((size_t)(CW + 2) * K + (size_t)UCE_SPAN * K + 2 * UCE_SPAN) * sizeof(float);
+  // 19 classes: 59 KB.  Every K the forward accepts (<= UCE_KMAX = 32: 95 KB) has to run backward as well: above the default
+  // 64 KB limit of dynamic LDS the kernel (each instantiation for itself) asks for its size once (a CU of gfx950 has 160 KB)
+  ONDA_REQUIRE(lds <= 160 * 1024);
+  if (lds > 64 * 1024) {
+    static size_t granted = 0;
+    if (lds > granted) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(upsample_bwd_rows_kernel<Grad>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return (int)e;
+      granted = lds;
+    }
+  }
+  hipLaunchKernelGGL(upsample_bwd_rows_kernel<Grad>, dim3((w + CW - 1) / CW, B * H), dim3(256), lds, ONDA_STREAM(s), grad, logits, ldl,
+                     ws, B, h, w, K, H, W, sy, sx, 1.f / sx, CW);
+  hipLaunchKernelGGL(upsample_ce_bwd_cols_kernel, dim3(ew_grid((size_t)B * h * w * ldl)), dim3(256), 0, ONDA_STREAM(s), ws, dlogits,
+                     ldl, B, h, w, K, H, sy, 1.f / sy);
+  return ONDA_LAUNCH_RESULT();
 }
 
 }  // namespace
@@ -1000,27 +1004,7 @@ int64_t onda_upsample_ce_bwd_ws(int B, int w, int K, int H) { return (int64_t)B 
 int onda_upsample_ce_bwd(const float* logits, int ldl, const uint8_t* labels, const float* result, const float* gscale, float w_ce,
                          float* dlogits, float* ws, int B, int h, int w, int K, int H, int W, onda_stream_t s) {
   ONDA_REQUIRE(logits && labels && result && dlogits && ws && K <= ldl && K <= UCE_KMAX && h > 1 && w > 1 && H > 1 && W > 1);
-  const float sy = ac_scale(h, H), sx = ac_scale(w, W);
-  const int CW = uce_block_cols(w, W);
-  ONDA_REQUIRE(CW >= 1);
-  const size_t lds = ((size_t)(CW + 2) * K + (size_t)UCE_SPAN * K + 2 * UCE_SPAN) * sizeof(float);
-  // 19 classes: 59 KB.  Every K the forward accepts (<= UCE_KMAX = 32: 95 KB) has to run backward as well (round-4 advisor): above
-  // the default 64 KB limit of dynamic LDS the kernel asks for its size once (a CU of gfx950 has 160 KB)
-  ONDA_REQUIRE(lds <= 160 * 1024);
-  if (lds > 64 * 1024) {
-    static size_t granted = 0;
-    if (lds > granted) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(upsample_ce_bwd_rows_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      granted = lds;
-    }
-  }
-  hipLaunchKernelGGL(upsample_ce_bwd_rows_kernel, dim3((w + CW - 1) / CW, B * H), dim3(256), lds, ONDA_STREAM(s), logits, ldl, labels,
-                     result, gscale, w_ce, ws, B, h, w, K, H, W, sy, sx, 1.f / sx, CW);
-  hipLaunchKernelGGL(upsample_ce_bwd_cols_kernel, dim3(ew_grid((size_t)B * h * w * ldl)), dim3(256), 0, ONDA_STREAM(s), ws, dlogits,
-                     ldl, B, h, w, K, H, sy, 1.f / sy);
-  return ONDA_LAUNCH_RESULT();
+  return upsample_bwd_two_pass(CeGrad{labels, result, gscale, w_ce}, logits, ldl, dlogits, ws, B, h, w, K, H, W, s);
 }
 
 int onda_upsample_entropy_fwd(const float* logits, int ldl, float* out, int B, int h, int w, int K, int H, int W, onda_stream_t s) {
@@ -1038,38 +1022,19 @@ int64_t onda_upsample_entropy_bwd_ws(int B, int w, int K, int H, int W) {
 int onda_upsample_entropy_bwd(const float* logits, int ldl, const float* dout, float* dlogits, float* ws, int B, int h, int w, int K,
                               int H, int W, onda_stream_t s) {
   ONDA_REQUIRE(logits && dout && dlogits && ws && K >= 2 && K <= ldl && K <= UCE_KMAX && B >= 1 && h > 1 && w > 1 && H > 1 && W > 1);
-  const float sy = ac_scale(h, H), sx = ac_scale(w, W), log2k = (float)log2((double)K);
-  const int CW = uce_block_cols(w, W);
-  if (CW < 1) {
-    // past what pass A's span takes: per-pixel gradient into ws[B][K][H][W], then the plain upsample gather (which leaves the
-    // padding columns alone: zero the rows first)
-    if (ldl > K) {
-      const hipError_t e = hipMemsetAsync(dlogits, 0, (size_t)B * h * w * ldl * sizeof(float), ONDA_STREAM(s));
-      if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL((upsample_entropy_kernel<true>), dim3(ew_grid((size_t)B * H * W)), dim3(256), 0, ONDA_STREAM(s), logits, ldl,
-                       dout, ws, B, h, w, K, H, W, sy, sx, log2k);
-    hipLaunchKernelGGL(upsample_bwd_kernel, dim3(ew_grid((size_t)B * h * w * K)), dim3(256), 0, ONDA_STREAM(s), ws, dlogits, ldl, B,
-                       h, w, K, H, W, sy, sx, 1.f / sy, 1.f / sx);
-    return ONDA_LAUNCH_RESULT();
+  const float log2k = (float)log2((double)K);
+  if (uce_block_cols(w, W) >= 1) return upsample_bwd_two_pass(EntGrad{dout, log2k}, logits, ldl, dlogits, ws, B, h, w, K, H, W, s);
+  // past what pass A's span takes: per-pixel gradient into ws[B][K][H][W], then the plain upsample gather (which leaves the
+  // padding columns alone: zero the rows first)
+  const float sy = ac_scale(h, H), sx = ac_scale(w, W);
+  if (ldl > K) {
+    const hipError_t e = hipMemsetAsync(dlogits, 0, (size_t)B * h * w * ldl * sizeof(float), ONDA_STREAM(s));
+    if (e != hipSuccess) return (int)e;
   }
-  // the LDS of upsample_ce_bwd_rows_kernel, byte for byte (the gradient vector comes from `dout` through registers, not
-  // through LDS): 59 KB at 19 classes, 95 KB at UCE_KMAX -- above 64 KB the kernel asks for its size once
-  const size_t lds = ((size_t)(CW + 2) * K + (size_t)UCE_SPAN * K + 2 * UCE_SPAN) * sizeof(float);
-  ONDA_REQUIRE(lds <= 160 * 1024);
-  if (lds > 64 * 1024) {
-    static size_t granted = 0;
-    if (lds > granted) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(upsample_entropy_bwd_rows_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      granted = lds;
-    }
-  }
-  hipLaunchKernelGGL(upsample_entropy_bwd_rows_kernel, dim3((w + CW - 1) / CW, B * H), dim3(256), lds, ONDA_STREAM(s), logits, ldl,
-                     dout, ws, B, h, w, K, H, W, sy, sx, 1.f / sx, CW, log2k);
-  hipLaunchKernelGGL(upsample_ce_bwd_cols_kernel, dim3(ew_grid((size_t)B * h * w * ldl)), dim3(256), 0, ONDA_STREAM(s), ws, dlogits,
-                     ldl, B, h, w, K, H, sy, 1.f / sy);
+  hipLaunchKernelGGL((upsample_entropy_kernel<true>), dim3(ew_grid((size_t)B * H * W)), dim3(256), 0, ONDA_STREAM(s), logits, ldl,
+                     dout, ws, B, h, w, K, H, W, sy, sx, log2k);
+  hipLaunchKernelGGL(upsample_bwd_kernel, dim3(ew_grid((size_t)B * h * w * K)), dim3(256), 0, ONDA_STREAM(s), ws, dlogits, ldl, B,
+                     h, w, K, H, W, sy, sx, 1.f / sy, 1.f / sx);
   return ONDA_LAUNCH_RESULT();
 }
 
