@@ -2,7 +2,6 @@
 // gradient, prototype distances / pseudo-labels, prototype statistics and EMA, plus the
 // multi-tensor SGD and teacher-EMA updates.  All HBM-bound; reductions are two-stage with a
 // fixed order (bitwise reproducible).
-#include <cstdlib>
 #include "common.h"
 
 namespace {
@@ -22,6 +21,85 @@ __global__ void sum_partials_kernel(const float* __restrict__ ws, int nblocks, i
   if (lane == 0) result[j] = (float)(s * (double)scale);
 }
 
+// ---- one pixel's class vector: the steps the loss kernels share ---------------------------------------------------------
+// v[0..K) = the row's logits; returns their maximum
+__device__ __forceinline__ float load_row_max(const float* __restrict__ row, int K, float* v) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k)
+    if (k < K) {
+      v[k] = row[k];
+      m = fmaxf(m, v[k]);
+    }
+  return m;
+}
+
+// sum_k exp(v[k] - m), and what stays in v[k]: the logit, exp(v - m), or v - m.  seg_loss forms log p = v - (m + log sum) from
+// the logits; target_loss forms p = exp(v - m) / sum and log p = (v - m) - log(sum) from the shifted logits, as softmax /
+// log_softmax do: v - (m + log(sum)) would carry the rounding of m + log(sum) (an ulp of the largest logit) into every p
+enum { KEEP_LOGIT, KEEP_EXP, KEEP_SHIFTED };
+template <int KEEP>
+__device__ __forceinline__ float exp_sum_row(float* v, float m, int K) {
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k)
+    if (k < K) {
+      const float x = v[k] - m, e = expf(x);
+      if constexpr (KEEP == KEEP_EXP) v[k] = e;
+      if constexpr (KEEP == KEEP_SHIFTED) v[k] = x;
+      sum += e;
+    }
+  return sum;
+}
+
+// a hard label: cls is compared with class indices; valid = enters CE; mask = not the ignore value (enters RCE and JS)
+struct PixelLabel {
+  int cls;
+  bool valid, mask;
+};
+__device__ __forceinline__ PixelLabel classify(int64_t tl, int K) {
+  return {(int)tl, tl >= 0 && tl != 255 && tl < K, tl != 255};
+}
+
+// CE and RCE in the gradient: coefficients from the upstream gradient and the forward pass' pixel counts, and one class' term
+struct CeRceCoef {
+  float ce, rce;
+};
+__device__ __forceinline__ CeRceCoef ce_rce_coef(float gs, float w_ce, float w_rce, float nvalid, float nmask) {
+  return {nvalid > 0.f ? gs * w_ce / nvalid : 0.f, gs * w_rce * (-LOG_CLAMP) / (nmask + 1e-6f)};
+}
+__device__ __forceinline__ float ce_rce_grad(CeRceCoef a, PixelLabel l, int k, float p, float pt) {
+  const float onehot = (k == l.cls) ? 1.f : 0.f;
+  float g = 0.f;
+  if (l.valid) g += a.ce * (p - onehot);
+  if (l.mask) g += a.rce * pt * (p - onehot);
+  return g;
+}
+
+// ws[block][j] = sum of part[j] over the block's 256 threads, j < NV <= 8: wave sums, one barrier, the four added in wave order
+template <int NV>
+__device__ __forceinline__ void block_partials(const float (&part)[NV], float* red, float* __restrict__ ws) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const float r = wave_sum(part[j]);
+    if (lane == 0) red[j * 4 + wave] = r;
+  }
+  __syncthreads();
+  if (threadIdx.x < NV) {
+    const int j = threadIdx.x;
+    ws[(size_t)blockIdx.x * 8 + j] = red[j * 4 + 0] + red[j * 4 + 1] + red[j * 4 + 2] + red[j * 4 + 3];
+  }
+}
+
+// s[j] = sum over blocks of ws[block][j], in block order, in double
+template <int NV>
+__device__ __forceinline__ void sum_block_partials(const float* __restrict__ ws, int nblocks, double (&s)[NV]) {
+  for (int j = 0; j < NV; ++j) s[j] = 0.0;
+  for (int b = 0; b < nblocks; ++b)
+    for (int j = 0; j < NV; ++j) s[j] += (double)ws[(size_t)b * 8 + j];
+}
+
 // ---- softmax statistics ----------------------------------------------------------------------
 __global__ __launch_bounds__(256) void softmax_stats_kernel(const float* __restrict__ logits, int ldl,
                                                             float* __restrict__ probs, int ldp,
@@ -36,7 +114,7 @@ __global__ __launch_bounds__(256) void softmax_stats_kernel(const float* __restr
     float m = -INFINITY;
     int am = 0;
 #pragma unroll
-    for (int k = 0; k < KMAX; ++k)
+    for (int k = 0; k < KMAX; ++k)  // (not load_row_max: the first maximum with its index, by comparison)
       if (k < K) {
         v[k] = row[k];
         if (v[k] > m) {
@@ -44,13 +122,7 @@ __global__ __launch_bounds__(256) void softmax_stats_kernel(const float* __restr
           am = k;
         }
       }
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < K) {
-        v[k] = expf(v[k] - m);
-        sum += v[k];
-      }
+    const float sum = exp_sum_row<KEEP_EXP>(v, m, K);
     const float inv = 1.f / sum;
     if (probs) {
 #pragma unroll
@@ -68,59 +140,37 @@ __global__ __launch_bounds__(256) void softmax_stats_kernel(const float* __restr
 __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float* __restrict__ logits, int ldl,
                                                            const int64_t* __restrict__ labels,
                                                            float* __restrict__ ws, int64_t N, int K) {
-  __shared__ float red[4];
+  __shared__ float red[5 * 4];
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  float ce = 0.f, rce = 0.f, kld = 0.f, nv = 0.f, nm = 0.f;
+  float part[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  // ce, rce, kld, n_valid, n_mask
   if (n < N) {
-    const float* row = logits + (size_t)n * ldl;
     float v[KMAX];
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < K) {
-        v[k] = row[k];
-        m = fmaxf(m, v[k]);
-      }
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < K) sum += expf(v[k] - m);
-    const float lse = m + logf(sum);
-    const int64_t tl = labels[n];
-    const bool valid = tl >= 0 && tl != 255 && tl < K;
-    const bool mask = tl != 255;
-    float others = 0.f;
+    const float m = load_row_max(logits + (size_t)n * ldl, K, v);
+    const float lse = m + logf(exp_sum_row<KEEP_LOGIT>(v, m, K));
+    const PixelLabel l = classify(labels[n], K);
+    float ce = 0.f, kld = 0.f, others = 0.f;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)
       if (k < K) {
         const float lp = v[k] - lse;
         kld -= lp;
-        if (valid && k == (int)tl) ce = -lp;
-        if (mask && k != (int)tl) others += expf(lp);
+        if (l.valid && k == l.cls) ce = -lp;
+        if (l.mask && k != l.cls) others += expf(lp);
       }
-    rce = mask ? -LOG_CLAMP * others : 0.f;
-    nv = valid ? 1.f : 0.f;
-    nm = mask ? 1.f : 0.f;
+    part[0] = ce;
+    part[1] = l.mask ? -LOG_CLAMP * others : 0.f;
+    part[2] = kld;
+    part[3] = l.valid ? 1.f : 0.f;
+    part[4] = l.mask ? 1.f : 0.f;
   }
-  float r;
-  r = block_sum_256(ce, red);
-  if (threadIdx.x == 0) ws[(size_t)blockIdx.x * 8 + 0] = r;
-  r = block_sum_256(rce, red);
-  if (threadIdx.x == 0) ws[(size_t)blockIdx.x * 8 + 1] = r;
-  r = block_sum_256(kld, red);
-  if (threadIdx.x == 0) ws[(size_t)blockIdx.x * 8 + 2] = r;
-  r = block_sum_256(nv, red);
-  if (threadIdx.x == 0) ws[(size_t)blockIdx.x * 8 + 3] = r;
-  r = block_sum_256(nm, red);
-  if (threadIdx.x == 0) ws[(size_t)blockIdx.x * 8 + 4] = r;
+  block_partials(part, red, ws);
 }
 
 __global__ void seg_loss_finalize_kernel(const float* __restrict__ ws, int nblocks, double total_elems,
                                          float* __restrict__ result) {
   if (threadIdx.x != 0) return;
-  double s[5] = {0, 0, 0, 0, 0};
-  for (int b = 0; b < nblocks; ++b)
-    for (int j = 0; j < 5; ++j) s[j] += (double)ws[(size_t)b * 8 + j];
+  double s[5];
+  sum_block_partials(ws, nblocks, s);
   result[0] = (float)(s[0] / s[3]);  // mean over kept pixels; 0/0 = NaN as in the reference
   result[1] = (float)(s[1] / (s[4] + 1e-6));
   result[2] = (float)(s[2] / total_elems);
@@ -136,47 +186,25 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restri
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
   const float gs = gscale ? gscale[0] : 1.f;
-  const float nvalid = result[3], nmask = result[4];
-  const float a_ce = nvalid > 0.f ? gs * w_ce / nvalid : 0.f;
-  const float a_rce = gs * w_rce * (-LOG_CLAMP) / (nmask + 1e-6f);
+  const CeRceCoef coef = ce_rce_coef(gs, w_ce, w_rce, result[3], result[4]);
   const float a_reg = gs * w_reg / ((float)N * (float)K);
-  const float* row = logits + (size_t)n * ldl;
   float v[KMAX];
-  float m = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k)
-    if (k < K) {
-      v[k] = row[k];
-      m = fmaxf(m, v[k]);
-    }
-  float sum = 0.f;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k)
-    if (k < K) {
-      v[k] = expf(v[k] - m);
-      sum += v[k];
-    }
-  const int64_t tl = labels[n];
-  const bool valid = tl >= 0 && tl != 255 && tl < K;
-  const bool mask = tl != 255;
+  const float m = load_row_max(logits + (size_t)n * ldl, K, v);
+  const float sum = exp_sum_row<KEEP_EXP>(v, m, K);
+  const PixelLabel l = classify(labels[n], K);
   float pt = 0.f;
 #pragma unroll
   for (int k = 0; k < KMAX; ++k)
     if (k < K) {
       v[k] = v[k] / sum;
-      if (k == (int)tl) pt = v[k];
+      if (k == l.cls) pt = v[k];
     }
   float* out = dl + (size_t)n * ldl;
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) {
     if (k >= ldl) break;
     float g = 0.f;
-    if (k < K) {
-      const float onehot = (k == (int)tl) ? 1.f : 0.f;
-      if (valid) g += a_ce * (v[k] - onehot);
-      if (mask) g += a_rce * pt * (v[k] - onehot);
-      g += a_reg * ((float)K * v[k] - 1.f);
-    }
+    if (k < K) g = ce_rce_grad(coef, l, k, v[k], pt) + a_reg * ((float)K * v[k] - 1.f);
     out[k] = g;
   }
 }
@@ -200,72 +228,44 @@ __global__ __launch_bounds__(256) void target_loss_fwd_kernel(const float* __res
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
   float part[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // ce, rce, reg, js numerator, n_valid, n_mask
   if (n < N) {
-    const float* row = logits + (size_t)n * ldl;
     float v[KMAX];
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < K) {
-        v[k] = row[k];
-        m = fmaxf(m, v[k]);
-      }
-    // p = exp(v - m) / sum and log p = (v - m) - log(sum), as softmax / log_softmax form them: v - (m + log(sum)) would
-    // carry the rounding of m + log(sum) (an ulp of the largest logit) into every p
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < K) {
-        v[k] -= m;
-        sum += expf(v[k]);
-      }
+    const float m = load_row_max(logits + (size_t)n * ldl, K, v);
+    const float sum = exp_sum_row<KEEP_SHIFTED>(v, m, K);
     const float lsum = logf(sum);
-    const int64_t tl = labels[n];
-    const bool valid = tl >= 0 && tl != 255 && tl < K;
-    const bool mask = tl != 255;
-    const float fm = mask ? 1.f : 0.f;
+    const PixelLabel l = classify(labels[n], K);
+    const float fm = l.mask ? 1.f : 0.f;
     float ce = 0.f, others = 0.f, reg = 0.f, js = 0.f;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)
       if (k < K) {
         const float lp = v[k] - lsum;
         const float p = expf(v[k]) / sum;
-        if (valid && k == (int)tl) ce = -lp;
-        if (mask && k != (int)tl) others += p;
+        if (l.valid && k == l.cls) ce = -lp;
+        if (l.mask && k != l.cls) others += p;
         if (reg_kind == REG_MRKLD) reg -= lp;
         if (reg_kind == REG_MRENT) reg += p * lp;
-        const float y = (mask && k == (int)tl) ? 1.f : JS_FLOOR;
+        const float y = (l.mask && k == l.cls) ? 1.f : JS_FLOOR;
         const float mp = p * fm;
         const float a = (y + mp) / 2.f;
         js += -xlog2x(a) + (xlog2x(y) + xlog2x(mp)) / 2.f;
       }
     part[0] = ce;
-    part[1] = mask ? -LOG_CLAMP * others : 0.f;
+    part[1] = l.mask ? -LOG_CLAMP * others : 0.f;
     part[2] = reg;
     part[3] = js;
-    part[4] = valid ? 1.f : 0.f;
+    part[4] = l.valid ? 1.f : 0.f;
     part[5] = fm;
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    const float r = wave_sum(part[j]);
-    if (lane == 0) red[j * 4 + wave] = r;
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    const int j = threadIdx.x;
-    ws[(size_t)blockIdx.x * 8 + j] = red[j * 4 + 0] + red[j * 4 + 1] + red[j * 4 + 2] + red[j * 4 + 3];
-  }
+  block_partials(part, red, ws);
 }
 
-// result = {ce, rce, reg, js, n_valid, n_mask, total}; block partials summed in block order in double
+// result = {ce, rce, reg, js, n_valid, n_mask, total}
 __global__ void target_loss_finalize_kernel(const float* __restrict__ ws, int nblocks, int reg_kind, int64_t N, int K,
                                             float w_ce, float w_rce, float w_reg, float w_js,
                                             float* __restrict__ result) {
   if (threadIdx.x != 0) return;
-  double s[6] = {0, 0, 0, 0, 0, 0};
-  for (int b = 0; b < nblocks; ++b)
-    for (int j = 0; j < 6; ++j) s[j] += (double)ws[(size_t)b * 8 + j];
+  double s[6];
+  sum_block_partials(ws, nblocks, s);
   const double ce = s[0] / s[4];  // 0/0 = NaN as in the reference
   const double rce = s[1] / (s[5] + 1e-6);
   const double reg = reg_kind == REG_MRKLD ? s[2] / ((double)N * K) : reg_kind == REG_MRENT ? s[2] / (double)N : 0.0;
@@ -295,36 +295,20 @@ __global__ __launch_bounds__(256) void target_loss_bwd_kernel(const float* __res
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
   const float gs = gscale ? gscale[0] : 1.f;
-  const float nvalid = result[4], nmask = result[5];
-  const float a_ce = nvalid > 0.f ? gs * w_ce / nvalid : 0.f;
-  const float a_rce = gs * w_rce * (-LOG_CLAMP) / (nmask + 1e-6f);
+  const float nmask = result[5];
+  const CeRceCoef coef = ce_rce_coef(gs, w_ce, w_rce, result[4], nmask);
   const float a_reg = reg_kind == REG_MRKLD   ? gs * w_reg / ((float)N * (float)K)
                       : reg_kind == REG_MRENT ? gs * w_reg / (float)N
                                               : 0.f;
   // n_mask == 0 makes this +inf and the gradient NaN, as in the reference; without JS nothing of it is used
   const bool use_js = w_js != 0.f;
   const float a_js = use_js ? gs * w_js / (log2f((float)K) * nmask) : 0.f;
-  const float* row = logits + (size_t)n * ldl;
   float v[KMAX];
-  float m = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k)
-    if (k < K) {
-      v[k] = row[k];
-      m = fmaxf(m, v[k]);
-    }
-  float sum = 0.f;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k)
-    if (k < K) {
-      v[k] -= m;
-      sum += expf(v[k]);
-    }
+  const float m = load_row_max(logits + (size_t)n * ldl, K, v);
+  const float sum = exp_sum_row<KEEP_SHIFTED>(v, m, K);
   const float lsum = logf(sum);
-  const int64_t tl = labels[n];
-  const bool valid = tl >= 0 && tl != 255 && tl < K;
-  const bool mask = tl != 255;
-  const float fm = mask ? 1.f : 0.f;
+  const PixelLabel l = classify(labels[n], K);
+  const float fm = l.mask ? 1.f : 0.f;
   // r[k] = d(a_reg*MRENT + a_js*JS)/dp_k of this pixel; its softmax Jacobian is p_k (r_k - sum_j p_j r_j)
   float r[KMAX];
   float pt = 0.f, pr = 0.f;
@@ -333,10 +317,10 @@ __global__ __launch_bounds__(256) void target_loss_bwd_kernel(const float* __res
     if (k < K) {
       const float lp = v[k] - lsum;
       v[k] = expf(v[k]) / sum;  // p, as the forward pass has it
-      if (k == (int)tl) pt = v[k];
+      if (k == l.cls) pt = v[k];
       float rk = reg_kind == REG_MRENT ? a_reg * lp : 0.f;
       if (use_js) {
-        const float y = (mask && k == (int)tl) ? 1.f : JS_FLOOR;
+        const float y = (l.mask && k == l.cls) ? 1.f : JS_FLOOR;
         const float mp = v[k] * fm;
         const float a = (y + mp) / 2.f;
         rk += a_js * (0.5f * (dxlog2x(mp) - dxlog2x(a))) * fm;
@@ -350,9 +334,7 @@ __global__ __launch_bounds__(256) void target_loss_bwd_kernel(const float* __res
     if (k >= ldl) break;
     float g = 0.f;
     if (k < K) {
-      const float onehot = (k == (int)tl) ? 1.f : 0.f;
-      if (valid) g += a_ce * (v[k] - onehot);
-      if (mask) g += a_rce * pt * (v[k] - onehot);
+      g = ce_rce_grad(coef, l, k, v[k], pt);
       if (reg_kind == REG_MRKLD) g += a_reg * ((float)K * v[k] - 1.f);
       g += v[k] * (r[k] - pr);
     }
@@ -375,27 +357,106 @@ __global__ void proto_sigma_kernel(const float* __restrict__ proto, const float*
   sigma[ch] = sqrtf(gsq - gm * gm);
 }
 
+// ---- the steps the direct kernels share: one wave per pixel, lane l owns channels 4l..4l+3 (C == 256) ------------------------
+// sp[K][256] = the prototypes, for the whole workgroup of 256 threads (16-byte copies)
+__device__ __forceinline__ void stage_prototypes(float* sp, const float* __restrict__ proto, int K) {
+  for (int i = threadIdx.x; i < K * 64; i += 256) reinterpret_cast<f32x4*>(sp)[i] = reinterpret_cast<const f32x4*>(proto)[i];
+  __syncthreads();
+}
+// this lane's four sigmas; ones for the Euclidean metric
+__device__ __forceinline__ f32x4 lane_sigma(const float* __restrict__ sigma, int mahalanobis, int lane) {
+  f32x4 sg = {1.f, 1.f, 1.f, 1.f};
+  if (mahalanobis) sg = *reinterpret_cast<const f32x4*>(sigma + lane * 4);
+  return sg;
+}
+// |f - p_k| (per channel / sigma for Mahalanobis) over the wave's 256 channels, in every lane
+__device__ __forceinline__ float proto_distance(const f32x4 f, const f32x4 sg, int mahalanobis, const float* sp, int k, int lane) {
+  f32x4 df = f - reinterpret_cast<const f32x4*>(sp)[k * 64 + lane];
+  if (mahalanobis) df = df / sg;
+  return sqrtf(wave_sum(df[0] * df[0] + df[1] * df[1] + df[2] * df[2] + df[3] * df[3]));
+}
+
+// The posterior of one pixel from its K distances, in place: d[k] = softmax(-(d - dmin) / tau), times the prior when there is
+// one, renormalised.  conf = max softmax, prmax = max prior, best = the first maximum of the posterior at class arg, second =
+// the runner-up (RUNNER_UP only).  ONE definition for both assign kernels: the direct kernel redoes exactly the pixels the
+// MFMA kernel does not trust, and has to decide them the same way.
+struct Posterior {
+  float conf, prmax, best, second;
+  int arg;
+};
+template <bool RUNNER_UP>
+__device__ __forceinline__ Posterior posterior(float* d, float dmin, float tau, bool has_prior, const float* pr, int K) {
+  Posterior o = {0.f, 0.f, -INFINITY, -INFINITY, 0};
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k)
+    if (k < K) {
+      d[k] = expf(-(d[k] - dmin) / tau);
+      sum += d[k];
+    }
+  float psum = 0.f;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k)
+    if (k < K) {
+      float p = d[k] / sum;
+      o.conf = fmaxf(o.conf, p);
+      if (has_prior) {
+        o.prmax = fmaxf(o.prmax, pr[k]);
+        p *= pr[k];
+      }
+      d[k] = p;
+      psum += p;
+    }
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k)
+    if (k < K) {
+      d[k] = d[k] / psum;
+      if (d[k] > o.best) {
+        if constexpr (RUNNER_UP) o.second = o.best;
+        o.best = d[k];
+        o.arg = k;
+      } else if constexpr (RUNNER_UP) {
+        if (d[k] > o.second) o.second = d[k];
+      }
+    }
+  return o;
+}
+
+// ws[block][t] = sum over the workgroup's WAVES waves of the t-th of three per-wave values (held by lane 0), in wave order
+template <int WAVES>
+__device__ __forceinline__ void block_sum3(float a, float b, float c, float (*red)[WAVES], float* __restrict__ ws) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if (lane == 0) {
+    red[0][wave] = a;
+    red[1][wave] = b;
+    red[2][wave] = c;
+  }
+  __syncthreads();
+  if (t < 3) {
+    float s = 0.f;
+#pragma unroll
+    for (int w_ = 0; w_ < WAVES; ++w_) s += red[t][w_];
+    ws[(size_t)blockIdx.x * 3 + t] = s;
+  }
+}
+
 // The distance matrix by itself (prototype_handler.distance / mahalanobis_distance, :111-138): dist[n][k] = D[k] - min_k D,
-// the direct form of proto_assign_kernel; one wave per pixel.
+// the direct form of proto_assign_kernel.
 __global__ __launch_bounds__(256) void proto_distances_kernel(const float* __restrict__ feat, int ldf,
                                                               const float* __restrict__ proto,
                                                               const float* __restrict__ sigma, int mahalanobis,
                                                               float* __restrict__ dist, int64_t N, int K) {
   __shared__ __attribute__((aligned(16))) float sp[KMAX * 256];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  for (int i = t; i < K * 64; i += 256) reinterpret_cast<f32x4*>(sp)[i] = reinterpret_cast<const f32x4*>(proto)[i];
-  __syncthreads();
-  f32x4 sg = {1.f, 1.f, 1.f, 1.f};
-  if (mahalanobis) sg = *reinterpret_cast<const f32x4*>(sigma + lane * 4);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  stage_prototypes(sp, proto, K);
+  const f32x4 sg = lane_sigma(sigma, mahalanobis, lane);
   for (int64_t n = (int64_t)blockIdx.x * 4 + wave; n < N; n += (int64_t)gridDim.x * 4) {
     const f32x4 f = *reinterpret_cast<const f32x4*>(feat + (size_t)n * ldf + lane * 4);
-    float mine = 0.f, dmin = INFINITY;
+    float mine = 0.f, dmin = INFINITY;  // (no d[KMAX] here: lane k keeps the k-th distance only)
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)
       if (k < K) {
-        f32x4 df = f - reinterpret_cast<const f32x4*>(sp)[k * 64 + lane];
-        if (mahalanobis) df = df / sg;
-        const float d = sqrtf(wave_sum(df[0] * df[0] + df[1] * df[1] + df[2] * df[2] + df[3] * df[3]));
+        const float d = proto_distance(f, sg, mahalanobis, sp, k, lane);
         dmin = fminf(dmin, d);
         if (k == lane) mine = d;
       }
@@ -403,7 +464,6 @@ __global__ __launch_bounds__(256) void proto_distances_kernel(const float* __res
   }
 }
 
-// One wave per pixel; lane l owns channels 4l..4l+3 (C == 256).
 __global__ __launch_bounds__(256) void proto_assign_kernel(const float* __restrict__ feat, int ldf,
                                                            const float* __restrict__ prior, int ldp,
                                                            const float* __restrict__ proto,
@@ -415,11 +475,9 @@ __global__ __launch_bounds__(256) void proto_assign_kernel(const float* __restri
   // (list != nullptr: only the pixels list[0 .. *list_len) -- the close decisions of proto_assign_mfma_kernel)
   __shared__ __attribute__((aligned(16))) float sp[KMAX * 256];
   __shared__ float red[3][4];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  for (int i = t; i < K * 64; i += 256) reinterpret_cast<f32x4*>(sp)[i] = reinterpret_cast<const f32x4*>(proto)[i];
-  __syncthreads();
-  f32x4 sg = {1.f, 1.f, 1.f, 1.f};
-  if (mahalanobis) sg = *reinterpret_cast<const f32x4*>(sigma + lane * 4);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  stage_prototypes(sp, proto, K);
+  const f32x4 sg = lane_sigma(sigma, mahalanobis, lane);
   float a_conf = 0.f, a_soft = 0.f, a_prior = 0.f;
   const int64_t wstride = (int64_t)gridDim.x * 4;
   const int64_t count = list ? (int64_t)*list_len : N;
@@ -431,46 +489,11 @@ __global__ __launch_bounds__(256) void proto_assign_kernel(const float* __restri
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)
       if (k < K) {
-        f32x4 df = f - reinterpret_cast<const f32x4*>(sp)[k * 64 + lane];
-        if (mahalanobis) df = df / sg;
-        float s = df[0] * df[0] + df[1] * df[1] + df[2] * df[2] + df[3] * df[3];
-        s = wave_sum(s);
-        d[k] = sqrtf(s);
+        d[k] = proto_distance(f, sg, mahalanobis, sp, k, lane);
         dmin = fminf(dmin, d[k]);
       }
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < K) {
-        d[k] = expf(-(d[k] - dmin) / tau);
-        sum += d[k];
-      }
-    float conf = 0.f, psum = 0.f, prmax = 0.f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < K) {
-        float p = d[k] / sum;
-        conf = fmaxf(conf, p);
-        if (prior) {
-          const float pr = prior[(size_t)n * ldp + k];
-          prmax = fmaxf(prmax, pr);
-          p *= pr;
-        }
-        d[k] = p;
-        psum += p;
-      }
-    float best = -INFINITY;
-    int arg = 0;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < K) {
-        d[k] = d[k] / psum;
-        if (d[k] > best) {
-          best = d[k];
-          arg = k;
-        }
-      }
-    if (lane == 0) labels[n] = best < thresh ? 255 : arg;
+    const Posterior o = posterior<false>(d, dmin, tau, prior != nullptr, prior ? prior + (size_t)n * ldp : nullptr, K);
+    if (lane == 0) labels[n] = o.best < thresh ? 255 : o.arg;
     if (soft) {
       float mine = 0.f;
 #pragma unroll
@@ -478,17 +501,11 @@ __global__ __launch_bounds__(256) void proto_assign_kernel(const float* __restri
         if (k < K && k == lane) mine = d[k];
       if (lane < K) soft[(size_t)n * K + lane] = mine;
     }
-    a_conf += conf;
-    a_soft += best;
-    a_prior += prmax;
+    a_conf += o.conf;
+    a_soft += o.best;
+    a_prior += o.prmax;
   }
-  if (lane == 0) {
-    red[0][wave] = a_conf;
-    red[1][wave] = a_soft;
-    red[2][wave] = a_prior;
-  }
-  __syncthreads();
-  if (t < 3) ws[(size_t)blockIdx.x * 3 + t] = red[t][0] + red[t][1] + red[t][2] + red[t][3];
+  block_sum3(a_conf, a_soft, a_prior, red, ws);
 }
 
 // ---- the same assignment with the feature <-> prototype contraction on the matrix cores -------------------------------------
@@ -503,7 +520,6 @@ __global__ __launch_bounds__(256) void proto_assign_kernel(const float* __restri
 // not: its distances carry an absolute error of ~1e-5.  Decisions that close are not trusted: a pixel whose two largest
 // posteriors, or whose largest posterior and the threshold, lie within `margin` goes on a list and is redone by the
 // direct kernel (proto_assign_list_kernel); everything else -- labels, soft map, monitor sums -- is final here.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int PA_TS = 129, PA_PS = 257, PA_GS = 33;
 constexpr int PA_WAVES = 6;  // 33 KB of prototypes + 6 x 16.6 KB of feature tiles = 133 KB: one workgroup per CU; 1 536 waves
                              // take the 1 049 pixel blocks of a 65 x 129 x 4 grid in ONE round (four waves per CU: two)
@@ -611,71 +627,24 @@ __global__ __launch_bounds__(64 * PA_WAVES) void proto_assign_mfma_kernel(const 
           d[k] = sqrtf(fmaxf(f2 + pn[k] - 2.f * tile[l32 * PA_GS + k], 0.f));
           dmin = fminf(dmin, d[k]);
         }
-      float sum = 0.f;
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k)
-        if (k < K) {
-          d[k] = expf(-(d[k] - dmin) / tau);
-          sum += d[k];
-        }
-      float conf = 0.f, psum = 0.f, prmax = 0.f;
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k)
-        if (k < K) {
-          float pp = d[k] / sum;
-          conf = fmaxf(conf, pp);
-          if (prior) {
-            prmax = fmaxf(prmax, pr_[k]);
-            pp *= pr_[k];
-          }
-          d[k] = pp;
-          psum += pp;
-        }
-      float best = -INFINITY, second = -INFINITY;
-      int arg = 0;
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k)
-        if (k < K) {
-          d[k] = d[k] / psum;
-          if (d[k] > best) {
-            second = best;
-            best = d[k];
-            arg = k;
-          } else if (d[k] > second) {
-            second = d[k];
-          }
-        }
-      if (best - second < margin || fabsf(best - thresh) < margin || !(best == best)) {
+      const Posterior o = posterior<true>(d, dmin, tau, prior != nullptr, pr_, K);
+      if (o.best - o.second < margin || fabsf(o.best - thresh) < margin || !(o.best == o.best)) {
         flagged[atomicAdd(nflagged, 1)] = (int)n;  // redone in the direct form
       } else {
-        labels[n] = best < thresh ? 255 : arg;
+        labels[n] = o.best < thresh ? 255 : o.arg;
         if (soft) {
 #pragma unroll
           for (int k = 0; k < KMAX; ++k)
             if (k < K) soft[(size_t)n * K + k] = d[k];
         }
-        a_conf += conf;
-        a_soft += best;
-        a_prior += prmax;
+        a_conf += o.conf;
+        a_soft += o.best;
+        a_prior += o.prmax;
       }
     }
     __builtin_amdgcn_wave_barrier();
   }
-  a_conf = wave_sum(a_conf);
-  a_soft = wave_sum(a_soft);
-  a_prior = wave_sum(a_prior);
-  if (lane == 0) {
-    red[0][wave] = a_conf;
-    red[1][wave] = a_soft;
-    red[2][wave] = a_prior;
-  }
-  __syncthreads();
-  if (t < 3) {
-    float a = 0.f;
-#pragma unroll
-    for (int w_ = 0; w_ < PA_WAVES; ++w_) a += red[t][w_];
-    ws[(size_t)blockIdx.x * 3 + t] = a;
-  }
+  block_sum3(wave_sum(a_conf), wave_sum(a_soft), wave_sum(a_prior), red, ws);
 }
 
 constexpr int SUMS_BLOCKS = 256;
@@ -768,6 +737,19 @@ __device__ __forceinline__ int mt_entry_of(const E* __restrict__ table, int n, i
   return lo;
 }
 
+// The entry that owns this workgroup and its element range [i0, i1) of it
+template <class E>
+__device__ __forceinline__ E mt_block(const E* __restrict__ table, int n_entries, int64_t& i0, int64_t& i1) {
+  const E e = table[mt_entry_of(table, n_entries, blockIdx.x)];
+  i0 = (int64_t)(blockIdx.x - e.first_block) * MT_BLOCK;
+  i1 = i0 + MT_BLOCK < e.n ? i0 + MT_BLOCK : e.n;
+  return e;
+}
+// a full block of tensors that all start on a 16-byte boundary: four f32x4 per thread; anything else goes element by element
+__device__ __forceinline__ bool mt_vector_block(int64_t i0, int64_t i1, const void* a, const void* b, const void* c = nullptr) {
+  return ((reinterpret_cast<size_t>(a) | reinterpret_cast<size_t>(b) | reinterpret_cast<size_t>(c)) & 15) == 0 && i1 - i0 == MT_BLOCK;
+}
+
 __device__ __forceinline__ void sgd_one(float& p, float& b, float g, float lr, float momentum, float wd, int times, int fresh) {
   if (fresh) b = 0.f;
   for (int r = 0; r < times; ++r) {
@@ -781,10 +763,9 @@ __device__ __forceinline__ void sgd_one(float& p, float& b, float g, float lr, f
 // division never becomes a pass of its own over 184 MB)
 __global__ __launch_bounds__(256) void sgd_multi_kernel(const OndaSgdEntry* __restrict__ table, int n_entries, float momentum,
                                                         float wd, float grad_scale) {
-  const OndaSgdEntry e = table[mt_entry_of(table, n_entries, blockIdx.x)];
-  const int64_t i0 = (int64_t)(blockIdx.x - e.first_block) * MT_BLOCK, i1 = i0 + MT_BLOCK < e.n ? i0 + MT_BLOCK : e.n;
-  const bool vec = ((reinterpret_cast<size_t>(e.p) | reinterpret_cast<size_t>(e.g) | reinterpret_cast<size_t>(e.buf)) & 15) == 0;
-  if (vec && i1 - i0 == MT_BLOCK) {
+  int64_t i0, i1;
+  const OndaSgdEntry e = mt_block(table, n_entries, i0, i1);
+  if (mt_vector_block(i0, i1, e.p, e.g, e.buf)) {
 #pragma unroll
     for (int k = 0; k < MT_BLOCK / 1024; ++k) {
       const int64_t i = i0 + (k * 256 + threadIdx.x) * 4;
@@ -811,10 +792,9 @@ __global__ __launch_bounds__(256) void sgd_multi_kernel(const OndaSgdEntry* __re
 }
 
 __global__ __launch_bounds__(256) void ema_multi_kernel(const OndaEmaEntry* __restrict__ table, int n_entries) {
-  const OndaEmaEntry e = table[mt_entry_of(table, n_entries, blockIdx.x)];
-  const int64_t i0 = (int64_t)(blockIdx.x - e.first_block) * MT_BLOCK, i1 = i0 + MT_BLOCK < e.n ? i0 + MT_BLOCK : e.n;
-  const bool vec = ((reinterpret_cast<size_t>(e.k) | reinterpret_cast<size_t>(e.q)) & 15) == 0;
-  if (vec && i1 - i0 == MT_BLOCK) {
+  int64_t i0, i1;
+  const OndaEmaEntry e = mt_block(table, n_entries, i0, i1);
+  if (mt_vector_block(i0, i1, e.k, e.q)) {
 #pragma unroll
     for (int k = 0; k < MT_BLOCK / 1024; ++k) {
       const int64_t i = i0 + (k * 256 + threadIdx.x) * 4;
@@ -825,14 +805,20 @@ __global__ __launch_bounds__(256) void ema_multi_kernel(const OndaEmaEntry* __re
   for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) e.k[i] = e.k[i] * e.keep + e.q[i] * e.blend;
 }
 
+// The entry points with one thread per pixel: the argument checks they share; the grid of 256-thread workgroups, or 0
+int pixel_blocks(const float* logits, const void* out, int64_t N, int K) {
+  return logits && out && K >= 1 && K <= KMAX && N >= 1 ? (int)((N + 255) / 256) : 0;
+}
+bool is_regularizer(int r) { return r >= REG_NONE && r <= REG_MRENT; }
+
 }  // namespace
 
 extern "C" {
 
 int onda_softmax_stats(const float* logits, int ldl, float* probs, int ldp, int32_t* argmax, float* result, float* ws,
                        int64_t N, int K, onda_stream_t s) {
-  ONDA_REQUIRE(logits && result && ws && K >= 1 && K <= KMAX && N >= 1);
-  const int nb = (int)((N + 255) / 256);
+  const int nb = pixel_blocks(logits, result, N, K);
+  ONDA_REQUIRE(nb && ws);
   hipLaunchKernelGGL(softmax_stats_kernel, dim3(nb), dim3(256), 0, ONDA_STREAM(s), logits, ldl, probs, ldp, argmax, ws,
                      N, K);
   hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(64), 0, ONDA_STREAM(s), ws, nb, 1, (float)(1.0 / (double)N),
@@ -842,8 +828,8 @@ int onda_softmax_stats(const float* logits, int ldl, float* probs, int ldp, int3
 
 int onda_seg_loss_fwd(const float* logits, int ldl, const int64_t* labels, float* result, float* ws, int64_t N, int K,
                       onda_stream_t s) {
-  ONDA_REQUIRE(logits && labels && result && ws && K >= 1 && K <= KMAX && N >= 1);
-  const int nb = (int)((N + 255) / 256);
+  const int nb = pixel_blocks(logits, result, N, K);
+  ONDA_REQUIRE(nb && labels && ws);
   hipLaunchKernelGGL(seg_loss_fwd_kernel, dim3(nb), dim3(256), 0, ONDA_STREAM(s), logits, ldl, labels, ws, N, K);
   hipLaunchKernelGGL(seg_loss_finalize_kernel, dim3(1), dim3(64), 0, ONDA_STREAM(s), ws, nb, (double)N * K, result);
   return ONDA_LAUNCH_RESULT();
@@ -851,8 +837,8 @@ int onda_seg_loss_fwd(const float* logits, int ldl, const int64_t* labels, float
 
 int onda_seg_loss_bwd(const float* logits, int ldl, const int64_t* labels, const float* result, const float* gscale,
                       float w_ce, float w_rce, float w_reg, float* dlogits, int64_t N, int K, onda_stream_t s) {
-  ONDA_REQUIRE(logits && labels && result && dlogits && K >= 1 && K <= KMAX && ldl <= KMAX && N >= 1);
-  const int nb = (int)((N + 255) / 256);
+  const int nb = pixel_blocks(logits, dlogits, N, K);
+  ONDA_REQUIRE(nb && labels && result && ldl <= KMAX);
   hipLaunchKernelGGL(seg_loss_bwd_kernel, dim3(nb), dim3(256), 0, ONDA_STREAM(s), logits, ldl, labels, result, gscale,
                      w_ce, w_rce, w_reg, dlogits, N, K);
   return ONDA_LAUNCH_RESULT();
@@ -860,9 +846,8 @@ int onda_seg_loss_bwd(const float* logits, int ldl, const int64_t* labels, const
 
 int onda_target_loss_fwd(const float* logits, int ldl, const int64_t* labels, int regularizer, float w_ce, float w_rce,
                          float w_reg, float w_js, float* result, float* ws, int64_t N, int K, onda_stream_t s) {
-  ONDA_REQUIRE(logits && labels && result && ws && K >= 1 && K <= KMAX && ldl >= K && N >= 1 && regularizer >= REG_NONE &&
-               regularizer <= REG_MRENT);
-  const int nb = (int)((N + 255) / 256);
+  const int nb = pixel_blocks(logits, result, N, K);
+  ONDA_REQUIRE(nb && labels && ws && ldl >= K && is_regularizer(regularizer));
   hipLaunchKernelGGL(target_loss_fwd_kernel, dim3(nb), dim3(256), 0, ONDA_STREAM(s), logits, ldl, labels, regularizer, ws,
                      N, K);
   hipLaunchKernelGGL(target_loss_finalize_kernel, dim3(1), dim3(64), 0, ONDA_STREAM(s), ws, nb, regularizer, N, K, w_ce,
@@ -873,9 +858,8 @@ int onda_target_loss_fwd(const float* logits, int ldl, const int64_t* labels, in
 int onda_target_loss_bwd(const float* logits, int ldl, const int64_t* labels, int regularizer, float w_ce, float w_rce,
                          float w_reg, float w_js, const float* result, const float* gscale, float* dlogits, int64_t N,
                          int K, onda_stream_t s) {
-  ONDA_REQUIRE(logits && labels && result && dlogits && K >= 1 && K <= KMAX && ldl >= K && ldl <= KMAX && N >= 1 &&
-               regularizer >= REG_NONE && regularizer <= REG_MRENT);
-  const int nb = (int)((N + 255) / 256);
+  const int nb = pixel_blocks(logits, dlogits, N, K);
+  ONDA_REQUIRE(nb && labels && result && ldl >= K && ldl <= KMAX && is_regularizer(regularizer));
   hipLaunchKernelGGL(target_loss_bwd_kernel, dim3(nb), dim3(256), 0, ONDA_STREAM(s), logits, ldl, labels, regularizer,
                      result, gscale, w_ce, w_rce, w_reg, w_js, dlogits, N, K);
   return ONDA_LAUNCH_RESULT();
@@ -892,10 +876,12 @@ int onda_proto_sigma(const float* proto, const float* sqmean, const float* count
 // workspace of onda_proto_assign in units of 3 floats: partial sums of the MFMA pass (PA_GRID workgroups) and of the direct
 // pass over the close decisions (PA_LIST_GRID), the list itself (N ints) and its length
 constexpr int PA_GRID = 256, PA_LIST_GRID = 256;
-static bool proto_direct_only() { return false; }  // (true: every pixel in the direct form -- the round-1 path the MFMA contraction replaced)
+static int64_t pa_direct_blocks(int64_t N) {  // the direct form alone: a wave per pixel, 2048 workgroups at most
+  const int64_t nb = (N + 3) / 4;
+  return nb < 2048 ? nb : 2048;
+}
 int onda_proto_assign_blocks(int64_t N) {
-  int64_t nb = (N + 3) / 4;
-  if (nb > 2048) nb = 2048;
+  const int64_t nb = pa_direct_blocks(N);
   const int64_t mfma = PA_GRID + PA_LIST_GRID + (N + 4 + 2) / 3;
   return (int)(nb > mfma ? nb : mfma);
 }
@@ -906,9 +892,8 @@ int onda_proto_assign(const float* feat, int ldf, const float* prior, int ldp, c
   ONDA_REQUIRE(feat && proto && labels && result && ws && C == 256 && K >= 1 && K <= KMAX && N >= 1 && ldf % 4 == 0);
   ONDA_REQUIRE(!mahalanobis || sigma);
   if (!ONDA_ALIGNED16(feat) || !ONDA_ALIGNED16(proto)) return ONDA_EALIGN;
-  if (proto_direct_only() || N >= (1ll << 31)) {  // the direct form everywhere (measurement / fallback for huge N)
-    int64_t nb = (N + 3) / 4;
-    if (nb > 2048) nb = 2048;
+  if (N >= (1ll << 31)) {  // the direct form everywhere: the list of close decisions holds 32-bit pixel indices
+    const int64_t nb = pa_direct_blocks(N);
     hipLaunchKernelGGL(proto_assign_kernel, dim3((unsigned)nb), dim3(256), 0, ONDA_STREAM(s), feat, ldf, prior, ldp, proto, sigma,
                        mahalanobis, tau, thresh, labels, soft, ws, N, K, nullptr, nullptr);
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(192), 0, ONDA_STREAM(s), ws, (int)nb, 3, (float)(1.0 / (double)N),

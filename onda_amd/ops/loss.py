@@ -43,34 +43,46 @@ def logits_rows(out):
     return buf, HEAD_PAD, B * H * W, K
 
 
+def _loss_setup(ctx, out, labels):
+    """What the two fused losses' forward passes share: (rows, ld, N, K, labels i64[N], result f32[8], ws)."""
+    rows, ld, N, K = logits_rows(out)
+    labels = labels.reshape(-1).to(device=out.device, dtype=torch.int64).contiguous()
+    result = torch.empty(8, device=out.device, dtype=torch.float32)
+    ws = torch.empty(8 * (N // 256 + 1), device=out.device, dtype=torch.float32)
+    ctx.save_for_backward(rows, labels, result)
+    ctx.shape = tuple(out.shape)
+    ctx.set_materialize_grads(False)
+    return rows, ld, N, K, labels, result, ws
+
+
+def _loss_backward_setup(ctx, gtotal):
+    """What their backward passes share: (rows, labels, result, the upstream gradient as a device scalar, dl [B,H,W,ld])."""
+    rows, labels, result = ctx.saved_tensors
+    B, _, H, W = ctx.shape
+    dl = torch.empty(B, H, W, ctx.meta[0], device=rows.device, dtype=torch.float32)
+    return rows, labels, result, gtotal.reshape(1).to(torch.float32).contiguous(), dl
+
+
 class SegLossFn(torch.autograd.Function):
     """w_ce*CE + w_rce*RCE + w_reg*MRKLD over hard labels, one pass; returns
     (total, ce, rce, mrkld) with gradients flowing through `total` only."""
 
     @staticmethod
     def forward(ctx, out, labels, w_ce, w_rce, w_reg):
-        rows, ld, N, K = logits_rows(out)
-        labels = labels.reshape(-1).to(device=out.device, dtype=torch.int64).contiguous()
-        result = torch.empty(8, device=out.device, dtype=torch.float32)
-        ws = torch.empty(8 * (N // 256 + 1), device=out.device, dtype=torch.float32)
+        rows, ld, N, K, labels, result, ws = _loss_setup(ctx, out, labels)
         call("onda_seg_loss_fwd", _p(rows), ld, _p(labels), _p(result), _p(ws), N, K, _stream())
-        ctx.save_for_backward(rows, labels, result)
-        ctx.meta = (ld, N, K, w_ce, w_rce, w_reg, tuple(out.shape))
+        ctx.meta = (ld, N, K, w_ce, w_rce, w_reg)
         ce, rce, reg = result[0], result[1], result[2]
         total = w_ce * ce + w_rce * rce + w_reg * reg
         ctx.mark_non_differentiable(ce, rce, reg)
-        ctx.set_materialize_grads(False)
         return total, ce, rce, reg
 
     @staticmethod
     def backward(ctx, gtotal, _a, _b, _c):
         if gtotal is None:
             return None, None, None, None, None
-        rows, labels, result = ctx.saved_tensors
-        ld, N, K, w_ce, w_rce, w_reg, shape = ctx.meta
-        B, _, H, W = shape
-        dl = torch.empty(B, H, W, ld, device=rows.device, dtype=torch.float32)
-        g = gtotal.reshape(1).to(torch.float32).contiguous()
+        rows, labels, result, g, dl = _loss_backward_setup(ctx, gtotal)
+        ld, N, K, w_ce, w_rce, w_reg = ctx.meta
         call("onda_seg_loss_bwd", _p(rows), ld, _p(labels), _p(result), _p(g), w_ce, w_rce, w_reg, _p(dl), N, K,
              _stream())
         return dl[..., :K].permute(0, 3, 1, 2), None, None, None, None
@@ -91,28 +103,20 @@ class TargetLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, out, labels, w_ce, w_rce, w_reg, regularizer, w_js):
-        rows, ld, N, K = logits_rows(out)
-        labels = labels.reshape(-1).to(device=out.device, dtype=torch.int64).contiguous()
-        result = torch.empty(8, device=out.device, dtype=torch.float32)
-        ws = torch.empty(8 * (N // 256 + 1), device=out.device, dtype=torch.float32)
+        rows, ld, N, K, labels, result, ws = _loss_setup(ctx, out, labels)
         call("onda_target_loss_fwd", _p(rows), ld, _p(labels), regularizer, w_ce, w_rce, w_reg, w_js, _p(result), _p(ws),
              N, K, _stream())
-        ctx.save_for_backward(rows, labels, result)
-        ctx.meta = (ld, N, K, w_ce, w_rce, w_reg, regularizer, w_js, tuple(out.shape))
+        ctx.meta = (ld, N, K, w_ce, w_rce, w_reg, regularizer, w_js)
         ce, rce, reg, js, total = result[0], result[1], result[2], result[3], result[6].clone()
         ctx.mark_non_differentiable(ce, rce, reg, js)
-        ctx.set_materialize_grads(False)
         return total, ce, rce, reg, js
 
     @staticmethod
     def backward(ctx, gtotal, _a, _b, _c, _d):
         if gtotal is None:
             return None, None, None, None, None, None, None
-        rows, labels, result = ctx.saved_tensors
-        ld, N, K, w_ce, w_rce, w_reg, regularizer, w_js, shape = ctx.meta
-        B, _, H, W = shape
-        dl = torch.empty(B, H, W, ld, device=rows.device, dtype=torch.float32)
-        g = gtotal.reshape(1).to(torch.float32).contiguous()
+        rows, labels, result, g, dl = _loss_backward_setup(ctx, gtotal)
+        ld, N, K, w_ce, w_rce, w_reg, regularizer, w_js = ctx.meta
         call("onda_target_loss_bwd", _p(rows), ld, _p(labels), regularizer, w_ce, w_rce, w_reg, w_js, _p(result), _p(g),
              _p(dl), N, K, _stream())
         return dl[..., :K].permute(0, 3, 1, 2), None, None, None, None, None, None
