@@ -509,13 +509,23 @@ __global__ __launch_bounds__(256) void proto_assign_kernel(const float* __restri
 }
 
 // ---- the same assignment with the feature <-> prototype contraction on the matrix cores -------------------------------------
-//   D^2[n][k] = |f_n/s|^2 - 2 (f_n/s).(p_k/s) + |p_k/s|^2,   the [N x 256] x [256 x K<=32] product on v_mfma_f32_32x32x2_f32
+//   D^2[n][k] = |g_n|^2 - 2 g_n.q_k + |q_k|^2,   g_n = (f_n - c)/s,   q_k = (p_k - c)/s,
+// with the [N x 256] x [256 x K<=32] product g.q on v_mfma_f32_32x32x2_f32
 // (fp32 operands, fp32 accumulate: exact products).  A wave takes 32 pixels: their scaled features are staged through LDS
 // in two 128-channel halves (coalesced 16-byte loads, rows padded to 129 floats: conflict-free operand reads), the scaled
 // prototypes live in LDS for the whole workgroup (rows of 257 floats).  K order: MFMA step s of a half multiplies channel
 // s (lanes 0-31) and channel 64+s (lanes 32-63) -- any order is a valid order of the sum.  The accumulator tile goes
 // through LDS once more so that lane p < 32 holds pixel p's K products and runs the softmax / prior / argmax / threshold
 // exactly like the direct kernel above.
+// c[256] is ONE point subtracted from every feature and every prototype before the expansion -- distances are translation-
+// invariant -- namely the unweighted mean of the K prototypes, summed per channel in class order by every workgroup (the same
+// bits in every workgroup and launch).  Without it the three terms have the size of |f/s|^2, and a common offset of the
+// channels (post-ReLU features have one) costs the difference ~2^-24 |f/s|^2 / D: 1e-3 of the soft map at an offset of 32.
+// Centred, the terms have the size of the spread around the prototypes.  What remains: the error scales with
+// |f - c|^2 / D, so a feature far from ALL prototypes and almost at one of them is still resolved worse than by the direct form.
+// The product of each 128-channel half is accumulated from zero and the two halves are added at the end: for a pixel at a
+// prototype g.q_k grows to |q_k|^2, and one chain over all 256 channels rounds at that size 128 times -- a Euclidean soft map
+// at 1.3e-5 of float64 where two chains of 64 steps stay at 4.8e-6 (tests/proto_fp64.py, case off32-eucl).
 // The expanded form cancels where the direct form (what the reference computes, prototype_handler.py:111-138) does
 // not: its distances carry an absolute error of ~1e-5.  Decisions that close are not trusted: a pixel whose two largest
 // posteriors, or whose largest posterior and the threshold, lie within `margin` goes on a list and is redone by the
@@ -535,15 +545,26 @@ __global__ __launch_bounds__(64 * PA_WAVES) void proto_assign_mfma_kernel(const 
                                                                 int64_t N, int K) {
   __shared__ float sm[32 * PA_PS + 32 + PA_WAVES * PA_WAVE_FLOATS];
   __shared__ float red[3][PA_WAVES];
-  float* ph = sm;                // [32][PA_PS]: prototypes / sigma, rows >= K zero
+  __shared__ __attribute__((aligned(16))) float cen[256];  // c: the unweighted mean prototype
+  float* ph = sm;                // [32][PA_PS]: (prototypes - c) / sigma, rows >= K zero
   float* pn = sm + 32 * PA_PS;   // [32]: their squared norms
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   float* tile = pn + 32 + wave * PA_WAVE_FLOATS;  // [32][PA_TS], later the product tile [32][PA_GS]
   for (int i = t; i < 32 * 256; i += 64 * PA_WAVES) {
     const int k = i >> 8, ch = i & 255;
-    float v = 0.f;
-    if (k < K) v = mahalanobis ? proto[k * 256 + ch] / sigma[ch] : proto[k * 256 + ch];
-    ph[k * PA_PS + ch] = v;
+    ph[k * PA_PS + ch] = k < K ? proto[k * 256 + ch] : 0.f;
+  }
+  __syncthreads();
+  if (t < 256) {  // one thread per channel, classes in order: every workgroup of every launch gets the same c
+    float a = 0.f;
+    for (int k = 0; k < K; ++k) a += ph[k * PA_PS + t];
+    cen[t] = a / (float)K;
+  }
+  __syncthreads();
+  for (int i = t; i < K * 256; i += 64 * PA_WAVES) {
+    const int k = i >> 8, ch = i & 255;
+    const float v = ph[k * PA_PS + ch] - cen[ch];
+    ph[k * PA_PS + ch] = mahalanobis ? v / sigma[ch] : v;
   }
   __syncthreads();
   if (t < 256) {  // squared norms: 8 threads per class, 32 channels each, fixed order
@@ -563,7 +584,7 @@ __global__ __launch_bounds__(64 * PA_WAVES) void proto_assign_mfma_kernel(const 
   for (int64_t blk = (int64_t)blockIdx.x * PA_WAVES + wave; blk < nblocks; blk += (int64_t)gridDim.x * PA_WAVES) {
     const int64_t n0 = blk * 32;
     float f2 = 0.f;  // lanes 0-31: squared norm of pixel l32's scaled features
-    f32x16 acc;
+    f32x16 acc, acc_h0;  // each 128-channel half accumulates from zero (see the header comment); acc_h0 keeps the first
 #pragma unroll
     for (int v = 0; v < 16; ++v) acc[v] = 0.f;
     // this lane's pixel's priors, requested now, used after the contraction
@@ -577,6 +598,7 @@ __global__ __launch_bounds__(64 * PA_WAVES) void proto_assign_mfma_kernel(const 
     for (int half = 0; half < 2; ++half) {
       f32x4 sg = {1.f, 1.f, 1.f, 1.f};  // 1 / sigma (a reciprocal, not the direct kernel's division: close decisions are redone there)
       if (mahalanobis) sg = f32x4{1.f, 1.f, 1.f, 1.f} / *reinterpret_cast<const f32x4*>(sigma + half * 128 + l32 * 4);
+      const f32x4 cv = *reinterpret_cast<const f32x4*>(cen + half * 128 + l32 * 4);
       // stage 32 pixels x 128 channels: a 16-byte load per lane covers two pixel rows per instruction; all 16 loads of
       // the half go out before the first is used (a wave has about one block: nothing else hides the latency)
       f32x4 fv[16];
@@ -589,7 +611,7 @@ __global__ __launch_bounds__(64 * PA_WAVES) void proto_assign_mfma_kernel(const 
 #pragma unroll
       for (int it = 0; it < 16; ++it) {
         const int row = 2 * it + half_lane;
-        const f32x4 v = fv[it] * sg;
+        const f32x4 v = (fv[it] - cv) * sg;
         float* dst = tile + row * PA_TS + l32 * 4;
         dst[0] = v[0];
         dst[1] = v[1];
@@ -612,7 +634,14 @@ __global__ __launch_bounds__(64 * PA_WAVES) void proto_assign_mfma_kernel(const 
 #pragma unroll 8
       for (int s_ = 0; s_ < 64; ++s_) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[s_], bp[s_], acc, 0, 0, 0);
       __builtin_amdgcn_wave_barrier();
+      if (half == 0) {
+        acc_h0 = acc;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+      }
     }
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[v] += acc_h0[v];
     // accumulator (row 8*(v/4) + 4*(lane/32) + v%4, column lane%32) -> [pixel][class] in LDS
 #pragma unroll
     for (int v = 0; v < 16; ++v) tile[(8 * (v >> 2) + 4 * half_lane + (v & 3)) * PA_GS + l32] = acc[v];
@@ -891,7 +920,7 @@ int onda_proto_assign(const float* feat, int ldf, const float* prior, int ldp, c
                       int64_t N, int C, int K, onda_stream_t s) {
   ONDA_REQUIRE(feat && proto && labels && result && ws && C == 256 && K >= 1 && K <= KMAX && N >= 1 && ldf % 4 == 0);
   ONDA_REQUIRE(!mahalanobis || sigma);
-  if (!ONDA_ALIGNED16(feat) || !ONDA_ALIGNED16(proto)) return ONDA_EALIGN;
+  if (!ONDA_ALIGNED16(feat) || !ONDA_ALIGNED16(proto) || (sigma && !ONDA_ALIGNED16(sigma))) return ONDA_EALIGN;
   if (N >= (1ll << 31)) {  // the direct form everywhere: the list of close decisions holds 32-bit pixel indices
     const int64_t nb = pa_direct_blocks(N);
     hipLaunchKernelGGL(proto_assign_kernel, dim3((unsigned)nb), dim3(256), 0, ONDA_STREAM(s), feat, ldf, prior, ldp, proto, sigma,

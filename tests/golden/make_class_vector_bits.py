@@ -13,7 +13,11 @@ kernel's partial sums changes from run to run; those means stay held by the tole
 test_prototypes_full_size.  Any other unstable key stops the recording.  tests/test_class_vector_bits.py recomputes `digests()`
 and compares every stable key.  Sound because every other kernel here sums in a fixed order; the block partials follow the
 launch grid, so the digests pin the host launches as well.  The fixture is recorded at a commit whose kernels are trusted
-(the parent of the change under test), never from the code under test.
+(the parent of the change under test), never from the code under test.  One exception so far, the change that made
+proto_assign_mfma_kernel centre features and prototypes on the mean prototype and accumulate each 128-channel half from zero: it
+changes the arithmetic of the soft map on purpose, so the 48 "proto soft" keys (and the 20 "proto means" keys that moved with
+them) were recorded from it, twice in separate processes, after every other key -- the 48 "proto labels" among them -- had been
+found equal to the parent's record; the new soft maps are held to float64 by tests/test_proto_fp64_parity.py.
 
 Inputs: CPU-seeded generators below, fixtures G4 (prototypes) and G16 (label patterns of test_target_regularisers.SMALL).
 """
