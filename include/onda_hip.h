@@ -159,6 +159,26 @@ void onda_debug_stamps(void* buffer);
  * over the image).  Replaces the stem's F.conv2d input side (deeplabv2.py:283) in "f16x2" pre-split mode. */
 int onda_stem_im2col_l2(const float* x_nchw, const float* xamax, void* dst, int64_t plane, int B, int H, int W, int Ho, int Wo,
                         int Kp, onda_stream_t s);
+/* ---- ADVENT's discriminator convolutions, 4 x 4 / stride 2 / pad 1 (csrc/disc.hip) -----------------------------------------
+ * Replaces nn.Conv2d(.., 4, 2, 1) [+ the nn.LeakyReLU(0.2) in front of it] of framework/model/discriminator.py:4-15 on the
+ * pre-split path.  Such a conv is the 2 x 2 / stride 1 / pad 0 conv of the space-to-depth view of the zero-padded input,
+ *   S[b, i, j, (py*2 + px)*C + c] = x[b, 2i + py - 1, 2j + px - 1, c] (0 outside),  Hs = H/2 + 1, Ws = W/2 + 1, Cp = 4C up to 32,
+ * with the weight w2[o, a, b, (py*2 + px)*C + c] = w[o, c, 2a + py, 2b + px]: forward, data gradient and weight gradient are
+ * onda_conv2d_fwd_l2 / onda_conv2d_wgrad_l2 with k = 2.  The two entry points are the passes around them.
+ * onda_s2d_split_h2: x fp32 (nchw != 0: [B,C,H,W]; else NHWC rows of ldx floats, C % 8 == 0) -> LeakyReLU(slope) (1 = none)
+ *   -> dst: limb rows [B*Hs*Ws][Cp/32][2][32] f16, channels 4C..Cp zero.  amax: max|x| of the source (onda_absmax or the
+ *   producer's epilogue); the scale is that BOUND (|slope| <= 1), no reduction over S.
+ * onda_d2s_bwd: gs fp32 [B*Hs*Ws][Cp], the gradient of S -> the gradient of x: border dropped, times 1 where x > 0 and slope
+ *   elsewhere (x == 0 included; x NULL = no activation).  nchw == 0: dst_limbs (limb rows [B*H*W][C/32][2][32], C % 32 == 0,
+ *   scaled by the bound *gamax = max|gs| as the data-gradient conv's yamax left it -- that buffer is the limb rows' max) and /
+ *   or dst_f32 (dense NHWC); either may be NULL, not both.  nchw != 0: x and dst_f32 are [B,C,H,W], dst_limbs NULL.
+ * ONDA_EINVAL: a null pointer, C <= 0, H or W < 2, B*Hs*Ws or B*H*W >= 2^31, a slope that is not finite or beyond [-1, 1], the
+ * channel rules above; ONDA_EALIGN: a pointer of a 16-byte access (every NHWC / limb-row operand) not 16-byte aligned.  No
+ * allocation, no synchronisation; nothing is launched when a check fails. */
+int onda_s2d_split_h2(const float* x, int nchw, int B, int C, int H, int W, int ldx, float slope, const float* amax, void* dst,
+                      onda_stream_t s);
+int onda_d2s_bwd(const float* gs, const float* gamax, const float* x, int nchw, int B, int C, int H, int W, int ldx, float slope,
+                 void* dst_limbs, float* dst_f32, onda_stream_t s);
 int onda_conv_l2_variant(int64_t M, int Cout);  /* base tile shape of an (M, Cout) problem: 0 256x128, 1 128x128, 2 256x64 */
 /* device kernel launched for a problem: 0 / 1 / 2 = conv_l2_kernel<4,2> / <2,2> / <4,1>, 3 = conv_l2x_kernel<4,2> (256x128 tiles,
  * at most 32 K-steps per tile: the continuous K-step stream); bench.py names its per-kernel figures after this.  Short K loops

@@ -57,6 +57,8 @@ SIGNATURES = {
     "onda_pack_blocks": (I, [I, I, I]),
     "onda_split_h2": (I, [P, L, I, I, P, I, L, P, P]),
     "onda_stem_im2col_l2": (I, [P, P, P, L, I, I, I, I, I, I, P]),
+    "onda_s2d_split_h2": (I, [P, I, I, I, I, I, I, F, P, P, P]),
+    "onda_d2s_bwd": (I, [P, P, P, I, I, I, I, I, I, F, P, P, P]),
     "onda_debug_stamps": (None, [P]),
     "onda_conv2d_fwd_l2_limbs": (I, [P, L, P, P, P, P, P, P, P, P, P]),
     "onda_switch_state_doubles": (I, [I]),

@@ -5,8 +5,9 @@ a supervised source pass, an adversarial target pass that asks the two discrimin
 What runs where.  The segmentation network is the HIP model.  ``loss_calc(interp(out), label)`` is ``ops.upsample_ce``.  Every
 ``d(prob_2_entropy(F.softmax(interp(out))))`` of the reference (:94-128) takes its map from ``ops.upsample_entropy``: the
 upsampled logits and the softmax never exist in memory, in either direction.  (The reference's ``F.softmax(x)`` has no
-``dim``; for a 4-D input torch's implicit choice is ``dim=1``, the class axis -- what the kernel computes.)  The discriminators
-are plain ``torch.nn`` (``framework/model/discriminator.py`` says why), Adam is torch's.
+``dim``; for a 4-D input torch's implicit choice is ``dim=1``, the class axis -- what the kernel computes.)  The discriminators'
+five 4x4 / stride 2 convolutions have a HIP route of their own, ``ops.disc_conv`` (``framework/model/discriminator.py`` says when
+``forward`` takes it and when the ``torch.nn`` module chain runs); Adam is torch's.
 
 The reference evaluates the expression six times a step with two heads: the discriminator pass recomputes the maps of
 ``pred.detach()``, which changes no number.  Here the target maps of the adversarial pass are reused, detached, and the source

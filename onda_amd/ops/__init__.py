@@ -11,7 +11,7 @@ Nothing here falls back to eager torch math: a missing library raises at first u
 import sys
 import types
 
-from . import _state, conv, core, limbs, loss, norm, tables
+from . import _state, conv, core, disc, limbs, loss, norm, tables
 from ._state import BN_EPS, GN_EPS, GN_GROUPS, HEAD_PAD, STEM_K
 
 # The switches live in `_state` (CONV_MODE, H2_PATH, GRAD_READY, PROFILE, PREDICATE, ROW_GROUPS, LIMB_ONLY, SHARE_GRADS,
@@ -20,7 +20,7 @@ _FLAGS = ("CONV_MODE", "H2_PATH", "GRAD_READY", "PROFILE", "PREDICATE", "ROW_GRO
 
 # everything else of the submodules under the names the single module had (tests, tools, bench.py and the framework mirror use
 # `ops.<name>`, underscore names included); to replace a function that OTHER ops code calls, patch it in its submodule
-for _m in (core, limbs, tables, conv, norm, loss):
+for _m in (core, limbs, tables, conv, norm, loss, disc):
     for _k, _v in vars(_m).items():
         if not _k.startswith("__") and _k not in _FLAGS and not isinstance(_v, types.ModuleType):
             globals()[_k] = _v

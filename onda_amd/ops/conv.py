@@ -191,13 +191,16 @@ def conv_forward(x, wp, k, stride, dil, pad, cout, out=None, scale=None, shift=N
     return out, stats, tiles
 
 
-def conv_dgrad(dy, wpd, k, stride, dil, pad, cin, in_hw, accumulate=None):
+def conv_dgrad(dy, wpd, k, stride, dil, pad, cin, in_hw, accumulate=None, yamax=None):
     """Data gradient.  dy NHWC [B,Ho,Wo,Cout(_pad)], wpd = pack_weight_dgrad(weight).
-    `accumulate`: a dense fp32 [B,Hi,Wi,cin] buffer the gradient is ADDED to (GradSink); returns it."""
+    `accumulate`: a dense fp32 [B,Hi,Wi,cin] buffer the gradient is ADDED to (GradSink); returns it.
+    `yamax`: zeroed amax floats that receive max|dx| from the epilogue (pre-split path, no `accumulate`)."""
     B, Ho, Wo, Co = dy.shape
     Hi, Wi = in_hw
     ldy = 0 if is_limb_only(dy) else nhwc_ld(dy)
     if accumulate is not None:
+        if yamax is not None:
+            raise RuntimeError("onda_amd: max|dx| from the data gradient's epilogue is not available with `accumulate`")
         fused = (stride == 1 and _use_l2(wpd, Co) and accumulate.is_contiguous() and accumulate.dtype == torch.float32
                  and tuple(accumulate.shape) == (B, Hi, Wi, cin) and not is_limb_only(accumulate))
         if not fused:
@@ -220,8 +223,10 @@ def conv_dgrad(dy, wpd, k, stride, dil, pad, cin, in_hw, accumulate=None):
     if _use_l2(wpd, Co):
         dyl = limbs_of(dy)
         d.ldx = dyl.ld
-        _launch_l2("dgrad", dyl, wpd, dx, d, tag_dims=(B * Ho * Wo if stride != 1 else B * Hi * Wi, cin, Co, k, stride, dil))
+        _launch_l2("dgrad", dyl, wpd, dx, d, yamax=yamax, tag_dims=(B * Ho * Wo if stride != 1 else B * Hi * Wi, cin, Co, k, stride, dil))
         return dx
+    if yamax is not None:
+        raise RuntimeError("onda_amd: max|dx| from the data gradient's epilogue needs the pre-split path")
     if is_limb_only(dy):
         raise RuntimeError("onda_amd: a limb-only gradient reached a data-gradient kernel that does not take limb planes")
     if isinstance(wpd, H2Weight):
