@@ -213,7 +213,12 @@ int onda_conv2d_fwd_l2(const void* xl, int64_t xplane, const float* xamax, const
  *   own batch statistics in one pass (the student's source-replay and target batches, prototypes.py:418-450, with the
  *   BN_POLICY "freeze" of adaptation_model.py:29-36: run_group = the group whose statistics move the running buffers, -1 =
  *   none); mean / invstd / xhat_amax are then [2][C].  finalize splits the one partial row that straddles the boundary
- *   with the conv output itself (y, row stride ldy; tile_rows = GEMM rows per partial row, onda_conv_l2_tiles_m_split). */
+ *   with the conv output itself (y, row stride ldy; tile_rows = GEMM rows per partial row, onda_conv_l2_tiles_m_split).
+ *   THE LAST TILE ROW (one group or two): the conv counts a tile's rows past M as zeros in its min / max.  Given tile_rows > 0
+ *   and y (ldy >= C; both optional without row groups: y == NULL or tile_rows == 0 keeps the table's extrema, which still
+ *   bound, only looser for a channel that lies on one side of zero), finalize takes the last tile row's extrema from its live
+ *   rows of y and leaves that tile row's table rows out -- after a hybrid stream-K schedule also its sub - 1 extra rows, the
+ *   last of the table.  onda_bn_train_l2 reads x as y. */
 int onda_bn_finalize_l2(const float* partials, int tiles, int C, int64_t count, float eps, float* mean, float* invstd,
                         float* running_mean, float* running_var, int64_t* nbt, float momentum, const float* gamma,
                         const float* beta, const float* res_amax, int relu, float* xhat_amax, float* out_amax, int64_t split,

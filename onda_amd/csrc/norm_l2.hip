@@ -152,11 +152,12 @@ __device__ __forceinline__ void grid_wait(float* amax_buf, int target) {
 // channels per 256-thread workgroup: thread t reads the 16-byte channel quad (t & 3) of the rows t >> 2, t >> 2 + 64, ...
 // (64-byte segments instead of the 4-byte, row-strided reads of a wave per channel: 16 times fewer cache-line requests
 // on tables of 0.5-3 MB), sums in double, folds the 16 row groups of a wave by butterfly and the four waves through
-// LDS.  Vector v < NS is summed, the others are folded by min (v == NS, only when MINMAX) or max.  The result of channel
+// LDS.  Vector v < NS is summed, the others are folded by min (v == NS, only when MINMAX) or max over the first `ext_rows` rows
+// but row `ext_skip`.  The result of channel
 // ch0 + c lands in thread c < 16 (`sum[v]`, `ext[v - NS]`).  Every thread must call; deterministic (fixed order).
 template <int NV, int NS, bool MINMAX>
 __device__ __forceinline__ void reduce_rows16(const float* __restrict__ partials, int rows, int C, int ch0, double (&sum)[NS > 0 ? NS : 1],
-                                              float (&ext)[NV - NS > 0 ? NV - NS : 1]) {
+                                              float (&ext)[NV - NS > 0 ? NV - NS : 1], int ext_rows, int ext_skip = -1) {
   constexpr int NE = NV - NS;
   __shared__ double lsum[4][NS > 0 ? NS : 1][16];
   __shared__ float lext[4][NE > 0 ? NE : 1][16];
@@ -187,7 +188,7 @@ __device__ __forceinline__ void reduce_rows16(const float* __restrict__ partials
       for (int v = 0; v < NE; ++v)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          x[v][j] = MINMAX && v == 0 ? fminf(x[v][j], val[NS + v][j]) : fmaxf(x[v][j], val[NS + v][j]);
+          if (r < ext_rows && r != ext_skip) x[v][j] = MINMAX && v == 0 ? fminf(x[v][j], val[NS + v][j]) : fmaxf(x[v][j], val[NS + v][j]);
     }
   }
 #pragma unroll
@@ -273,12 +274,55 @@ __device__ __forceinline__ void bn_finalize_block(const BnFinalizeArgs& a, const
     if (g == 0) nrows = ts; else row0 = ts, nrows = tiles - ts;
     count = g == 0 ? (double)split : count - (double)split;
   }
+  // THE LAST TILE ROW'S ROWS PAST M count as zeros in its extrema (conv_l2.hip l2_epilogue and conv_l2_fixup_kernel), and every
+  // feature grid of this network leaves such rows (M = 256 k + 4).  A zero is no value of a channel that lies on one side of
+  // zero: its xhat_amax would be |mean| * invstd instead of max|xhat| and the bound of max|out| would grow with it (a constant
+  // channel: by 1 / sqrt(eps)).  So the group that owns the last tile row takes that tile row's extrema from its live rows of y
+  // instead (16 row lanes x 16 channels, at most bm - 1 rows, 4 in this network; the loads are in flight while the table is
+  // reduced) and leaves the table rows of that tile row out of the extrema: row tilesM - 1, and after a hybrid stream-K
+  // schedule (l2_plan `balanced`: tilesM + rem_rows * (sub - 1) table rows, the remainder tile rows' sub-block rows behind the
+  // regular ones in tile-row order) its sub - 1 extra rows, the LAST ones of the table.  sub - 1 is 15 (128 x 128 and 256 x 64
+  // tiles) or 31 (256 x 128); it is read off the table: 128-row tiles have 15, otherwise the one that divides the extra rows.
+  // Where that does not decide (both divide, or neither: a table this rule does not know) the table's extrema stand as they
+  // are -- bounds all the same, only looser.
+  const long long m_all = (long long)a.count;
+  const int tiles_m = bm > 1 ? (int)((m_all + bm - 1) / bm) : tiles, extra = tiles - tiles_m;
+  int sub1 = 0;  // extra rows of one remainder tile row
+  bool known = y != nullptr && bm > 1 && extra >= 0;
+  if (known && extra > 0) {
+    const bool d15 = extra % 15 == 0 && extra / 15 <= tiles_m, d31 = bm == 256 && extra % 31 == 0 && extra / 31 <= tiles_m;
+    if (bm == 128 ? d15 : d15 != d31) sub1 = (bm == 128 || d15) ? 15 : 31; else known = false;
+  }
+  const long long last0 = (long long)(tiles_m - 1) * bm;
+  const bool rescan = known && last0 < m_all && m_all < last0 + bm && (split <= 0 || g == 1);
+  __shared__ float lmn[16][16], lmx[16][16];
+  if (rescan) {
+    const int c = threadIdx.x & 15, lane = threadIdx.x >> 4;
+    float mn = 3.0e38f, mx = -3.0e38f;
+    if (bx * 16 + c < C)
+      for (long long r = (split > last0 ? split : last0) + lane; r < m_all; r += 16) {
+        const float v = y[(size_t)r * ldy + bx * 16 + c];
+        mn = fminf(mn, v);
+        mx = fmaxf(mx, v);
+      }
+    lmn[lane][c] = mn;
+    lmx[lane][c] = mx;
+  }
   double sum[2];
   float ext[2];
-  reduce_rows16<4, 2, true>(partials + (size_t)row0 * 4 * C, nrows, C, bx * 16, sum, ext);
+  // (rows relative to row0; the barrier inside orders lmn / lmx)
+  reduce_rows16<4, 2, true>(partials + (size_t)row0 * 4 * C, nrows, C, bx * 16, sum, ext, rescan ? nrows - sub1 : nrows,
+                            rescan ? tiles_m - 1 - row0 : -1);
   const int ch = bx * 16 + threadIdx.x;
   float bound = 0.f;
   if (threadIdx.x < 16 && ch < C) {
+    if (rescan) {
+#pragma unroll
+      for (int l = 0; l < 16; ++l) {
+        ext[0] = fminf(ext[0], lmn[l][threadIdx.x]);
+        ext[1] = fmaxf(ext[1], lmx[l][threadIdx.x]);
+      }
+    }
     if (split > 0 && split % bm != 0) {  // the group-0 rows of the straddling tile
       double c1 = 0.0, c2 = 0.0;
       float mn = 3.0e38f, mx = -3.0e38f;
@@ -536,7 +580,7 @@ __device__ __forceinline__ void bn_bwd_sums_block(const BnBwdSumsArgs& a, const 
   const double inv_m = g == 0 ? a.inv_m0 : a.inv_m1;
   double sum[2];
   float ext[1];
-  reduce_rows16<3, 2, false>(a.partials + (size_t)row0 * 3 * C, nrows, C, bx * 16, sum, ext);
+  reduce_rows16<3, 2, false>(a.partials + (size_t)row0 * 3 * C, nrows, C, bx * 16, sum, ext, nrows);
   const int ch = bx * 16 + threadIdx.x;
   float bound = 0.f;
   if (threadIdx.x < 16 && ch < C) {
@@ -662,6 +706,7 @@ int onda_bn_finalize_l2(const float* partials, int tiles, int C, int64_t count, 
                         int tile_rows, int run_group, const float* y, int ldy, onda_stream_t s) {
   ONDA_REQUIRE(partials && mean && invstd && gamma && beta && xhat_amax && out_amax && tiles >= 1 && C >= 4 && C % 4 == 0 && count >= 1);
   ONDA_REQUIRE(split >= 0 && split < count && (split == 0 || (tile_rows > 0 && y && ldy >= C && split / tile_rows < tiles)));
+  ONDA_REQUIRE(y == nullptr || ldy >= C);  // (without row groups: y and tile_rows let the last tile's extrema skip its rows past M)
   if (!ONDA_ALIGNED16(partials)) return ONDA_EALIGN;
   hipLaunchKernelGGL(bn_finalize_l2_kernel, dim3((C + 15) / 16, split > 0 ? 2 : 1), dim3(256), 0, ONDA_STREAM(s),
                      finalize_args(partials, tiles, C, count, eps, mean, invstd, running_mean, running_var, nbt, momentum, gamma, beta,

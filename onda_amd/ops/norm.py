@@ -125,7 +125,9 @@ class BNTrainLimbFn(torch.autograd.Function):
         if res is not None and (res.ld != C or tuple(residual.shape) != (B, H, W, C)):
             raise RuntimeError("onda_amd: residual of a BatchNorm must be a dense [B,H,W,C] activation")
         out_amax = amax_slot(dev)
-        tile_rows = _stat_tile_rows(stats) if split else 0
+        # (one group: the tile height lets finalize take the last tile's extrema from its live rows; a partial table that did not
+        #  come from conv_forward has none, and keeps the extrema it carries)
+        tile_rows = _stat_tile_rows(stats) if split else getattr(stats, "_onda_tile_rows", 0)
         planes = torch.empty(2, M, C, device=dev, dtype=torch.float16)
         # [out > 0] as one bit per element for the backward passes (they would read 2 bytes of `planes` per element instead)
         mask = torch.empty(M * C // 8, device=dev, dtype=torch.uint8) if relu and any(ctx.needs_input_grad) else None
@@ -138,7 +140,7 @@ class BNTrainLimbFn(torch.autograd.Function):
         else:
             call("onda_bn_finalize_l2", _p(stats), stats.shape[0], C, M, BN_EPS, _p(mean), _p(invstd), _p(rm), _p(rv), _p(nbt),
                  float(momentum), _p(gamma), _p(beta), _p(res.amax) if res is not None else None, int(relu), _p(xhat_amax),
-                 _p(out_amax), split, tile_rows, 1, _p(y) if split else None, nhwc_ld(y) if split else 0, _stream())
+                 _p(out_amax), split, tile_rows, 1, _p(y), nhwc_ld(y), _stream())
             call("onda_bn_apply_l2", _p(y), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(res.planes) if res is not None else None,
                  res.plane if res is not None else 0, _p(res.amax) if res is not None else None, _p(planes), M * C, _p(out_amax),
                  M, C, int(relu), _p(mask), split, _stream())
