@@ -483,6 +483,26 @@ int onda_sgd_multi(const OndaSgdEntry* table, int n, float momentum, float weigh
 typedef struct OndaEmaEntry { float* k; const float* q; int64_t n; float keep; float blend; int first_block; } OndaEmaEntry;
 int onda_ema_multi(const OndaEmaEntry* table, int n, int64_t total_blocks, onda_stream_t s);
 
+/* ---- model regularisation (prototypes.py:81-91, :334-336; utils/ewc.py:47-54: the EWC penalty with unit Fisher
+ * weights that pulls the student towards the frozen static model).
+ * The VALUE: result[0] = (float)(half_lambda * sum over all entries and elements of (a - b)^2), differences and squares
+ * in float32, one float32 partial per workgroup in ws, the partials summed in a fixed order in double: the same bits on
+ * every run.  ws: onda_sqdiff_multi_ws(total_blocks) floats, the caller's.  Two launches, no synchronisation. */
+typedef struct OndaSqdiffEntry { const float* a; const float* b; int64_t n; int first_block; } OndaSqdiffEntry;
+int64_t onda_sqdiff_multi_ws(int64_t total_blocks);
+int onda_sqdiff_multi(const OndaSqdiffEntry* table, int n, float half_lambda, int64_t total_blocks, float* ws,
+                      float* result, onda_stream_t s);
+/* The GRADIENT never becomes a pass of its own: onda_sgd_anchor_multi is onda_sgd_multi with one more stream.  Where
+ * `anchor` is not NULL every element's gradient is formed once, from the parameter value the launch finds,
+ *   g' = fl(g * grad_scale + (-2 * fl(half_lambda * fl(anchor - p))))          (each fl one float32 rounding, no fma:
+ * what autograd leaves in .grad for the penalty under upstream 1), and the `times` updates replay that g'.  `g` may be
+ * NULL there (a parameter no loss reached: g = 0).  anchor == NULL: the entry is updated exactly as by onda_sgd_multi. */
+typedef struct OndaSgdAnchorEntry {
+  float* p; const float* g; float* buf; const float* anchor; int64_t n; float lr; int times; int fresh; int first_block;
+} OndaSgdAnchorEntry;
+int onda_sgd_anchor_multi(const OndaSgdAnchorEntry* table, int n, float momentum, float weight_decay, float grad_scale,
+                          float half_lambda, int64_t total_blocks, onda_stream_t s);
+
 /* ---- input pipeline -----------------------------------------------------------
  * Replaces the per-sample CPU work of framework/dataset/segmentation_db.py:56-99 (`__getitem__`,
  * `_load_img` base_dataset.py:89-95, `preprocess` :98-99, `color_mapper` func.py:88-115) AFTER the

@@ -36,6 +36,15 @@ class OndaSgdEntry(Structure):
                 ("times", c_int), ("fresh", c_int), ("first_block", c_int)]
 
 
+class OndaSgdAnchorEntry(Structure):
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("buf", c_void_p), ("anchor", c_void_p), ("n", c_int64), ("lr", c_float),
+                ("times", c_int), ("fresh", c_int), ("first_block", c_int)]
+
+
+class OndaSqdiffEntry(Structure):
+    _fields_ = [("a", c_void_p), ("b", c_void_p), ("n", c_int64), ("first_block", c_int)]
+
+
 class OndaPackEntry(Structure):
     _fields_ = [("w", c_void_p), ("fwd", c_void_p), ("dgrad", c_void_p), ("amax", c_void_p), ("Cout", c_int), ("Cin", c_int),
                 ("taps", c_int), ("first_block", c_int)]
@@ -135,6 +144,9 @@ SIGNATURES = {
     "onda_sgd_multi": (I, [P, I, F, F, F, L, P]),
     "onda_ema_multi": (I, [P, I, L, P]),
     "onda_multi_tensor_block": (I, []),
+    "onda_sqdiff_multi_ws": (L, [L]),
+    "onda_sqdiff_multi": (I, [P, I, F, L, P, P, P]),
+    "onda_sgd_anchor_multi": (I, [P, I, F, F, F, F, L, P]),
     "onda_resample_h_u8": (I, [P, P, I, I, I, P, P, I, P]),
     "onda_resample_v_norm": (I, [P, P, I, I, I, P, P, I, POINTER(c_float), POINTER(c_float), I, P]),
     "onda_resize_nearest_lut": (I, [P, P, I, I, I, P, P, P, P]),

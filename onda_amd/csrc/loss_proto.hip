@@ -820,6 +820,108 @@ __global__ __launch_bounds__(256) void sgd_multi_kernel(const OndaSgdEntry* __re
   }
 }
 
+// ---- EWC anchor (utils/ewc.py:47-54 with unit Fisher weights; prototypes.py:334-336) ----------------------------------------
+// The penalty's gradient, as autograd leaves it in .grad under upstream 1, added to the scaled gradient: three roundings and
+// one more for the sum, none of them fused (a fused multiply-add would skip the rounding of the product that ATen's
+// elementwise kernels make).  The factors -2 are exact.
+__device__ __forceinline__ float anchored_grad(float g, float grad_scale, float half_lambda, float anchor, float p) {
+#pragma clang fp contract(off)
+  const float d = anchor - p;
+  const float h = half_lambda * d;
+  const float c = -2.f * h;
+  const float gs = g * grad_scale;
+  return gs + c;
+}
+
+// One block of one entry.  ANCHORED = false is sgd_multi_kernel's body, expression for expression: an entry without an anchor
+// takes it, so that it is updated with the bits onda_sgd_multi gives it.
+template <bool ANCHORED>
+__device__ __forceinline__ void sgd_anchor_block(const OndaSgdAnchorEntry& e, int64_t i0, int64_t i1, float momentum, float wd,
+                                                 float grad_scale, float half_lambda) {
+  if (mt_vector_block(i0, i1, e.p, e.g, e.buf) && (!ANCHORED || (reinterpret_cast<size_t>(e.anchor) & 15) == 0)) {
+#pragma unroll
+    for (int k = 0; k < MT_BLOCK / 1024; ++k) {
+      const int64_t i = i0 + (k * 256 + threadIdx.x) * 4;
+      f32x4 p = *reinterpret_cast<const f32x4*>(e.p + i), b = e.fresh ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(e.buf + i);
+      const f32x4 g = !ANCHORED || e.g ? *reinterpret_cast<const f32x4*>(e.g + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+      f32x4 a = {0.f, 0.f, 0.f, 0.f};
+      if (ANCHORED) a = *reinterpret_cast<const f32x4*>(e.anchor + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float pj = p[j], bj = b[j];
+        if (ANCHORED)
+          sgd_one(pj, bj, anchored_grad(g[j], grad_scale, half_lambda, a[j], pj), e.lr, momentum, wd, e.times, e.fresh);
+        else
+          sgd_one(pj, bj, g[j] * grad_scale, e.lr, momentum, wd, e.times, e.fresh);
+        p[j] = pj;
+        b[j] = bj;
+      }
+      *reinterpret_cast<f32x4*>(e.p + i) = p;
+      *reinterpret_cast<f32x4*>(e.buf + i) = b;
+    }
+    return;
+  }
+  for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+    float p = e.p[i], b = e.fresh ? 0.f : e.buf[i];
+    if (ANCHORED)
+      sgd_one(p, b, anchored_grad(e.g ? e.g[i] : 0.f, grad_scale, half_lambda, e.anchor[i], p), e.lr, momentum, wd, e.times, e.fresh);
+    else
+      sgd_one(p, b, e.g[i] * grad_scale, e.lr, momentum, wd, e.times, e.fresh);
+    e.p[i] = p;
+    e.buf[i] = b;
+  }
+}
+
+__global__ __launch_bounds__(256) void sgd_anchor_multi_kernel(const OndaSgdAnchorEntry* __restrict__ table, int n_entries,
+                                                               float momentum, float wd, float grad_scale, float half_lambda) {
+  int64_t i0, i1;
+  const OndaSgdAnchorEntry e = mt_block(table, n_entries, i0, i1);
+  if (e.anchor)
+    sgd_anchor_block<true>(e, i0, i1, momentum, wd, grad_scale, half_lambda);
+  else
+    sgd_anchor_block<false>(e, i0, i1, momentum, wd, grad_scale, half_lambda);
+}
+
+// The penalty's value: one float32 partial per workgroup (differences and squares in float32, as the reference has them) ...
+__global__ __launch_bounds__(256) void sqdiff_multi_kernel(const OndaSqdiffEntry* __restrict__ table, int n_entries,
+                                                           float* __restrict__ ws) {
+  __shared__ float red[4];
+  int64_t i0, i1;
+  const OndaSqdiffEntry e = mt_block(table, n_entries, i0, i1);
+  float acc = 0.f;
+  if (mt_vector_block(i0, i1, e.a, e.b)) {
+#pragma unroll
+    for (int k = 0; k < MT_BLOCK / 1024; ++k) {
+      const int64_t i = i0 + (k * 256 + threadIdx.x) * 4;
+      const f32x4 d = *reinterpret_cast<const f32x4*>(e.a + i) - *reinterpret_cast<const f32x4*>(e.b + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc += d[j] * d[j];
+    }
+  } else {
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+      const float d = e.a[i] - e.b[i];
+      acc += d * d;
+    }
+  }
+  const float r = block_sum_256(acc, red);
+  if (threadIdx.x == 0) ws[blockIdx.x] = r;
+}
+// ... and their sum in a fixed order, in double: thread t takes the partials t, t + 256, ..., then a fixed tree over the threads
+__global__ __launch_bounds__(256) void sqdiff_finalize_kernel(const float* __restrict__ ws, int64_t nblocks, float half_lambda,
+                                                              float* __restrict__ result) {
+  __shared__ double sh[256];
+  const int t = threadIdx.x;
+  double s = 0.0;
+  for (int64_t b = t; b < nblocks; b += 256) s += (double)ws[b];
+  sh[t] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) sh[t] += sh[t + o];
+    __syncthreads();
+  }
+  if (t == 0) result[0] = (float)((double)half_lambda * sh[0]);
+}
+
 __global__ __launch_bounds__(256) void ema_multi_kernel(const OndaEmaEntry* __restrict__ table, int n_entries) {
   int64_t i0, i1;
   const OndaEmaEntry e = mt_block(table, n_entries, i0, i1);
@@ -998,6 +1100,24 @@ int onda_multi_tensor_block(void) { return MT_BLOCK; }
 int onda_ema_multi(const OndaEmaEntry* table, int n, int64_t max_n, onda_stream_t s) {
   ONDA_REQUIRE(table && n >= 1 && max_n >= 1 && max_n < (1ll << 31));  // max_n: total blocks (flat launch)
   hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)max_n), dim3(256), 0, ONDA_STREAM(s), table, n);
+  return ONDA_LAUNCH_RESULT();
+}
+
+int64_t onda_sqdiff_multi_ws(int64_t total_blocks) { return total_blocks > 0 ? total_blocks : 0; }
+
+int onda_sqdiff_multi(const OndaSqdiffEntry* table, int n, float half_lambda, int64_t max_n, float* ws, float* result,
+                      onda_stream_t s) {
+  ONDA_REQUIRE(table && ws && result && n >= 1 && max_n >= 1 && max_n < (1ll << 31));  // max_n: total blocks (flat launch)
+  hipLaunchKernelGGL(sqdiff_multi_kernel, dim3((unsigned)max_n), dim3(256), 0, ONDA_STREAM(s), table, n, ws);
+  hipLaunchKernelGGL(sqdiff_finalize_kernel, dim3(1), dim3(256), 0, ONDA_STREAM(s), ws, max_n, half_lambda, result);
+  return ONDA_LAUNCH_RESULT();
+}
+
+int onda_sgd_anchor_multi(const OndaSgdAnchorEntry* table, int n, float momentum, float weight_decay, float grad_scale,
+                          float half_lambda, int64_t max_n, onda_stream_t s) {
+  ONDA_REQUIRE(table && n >= 1 && max_n >= 1 && max_n < (1ll << 31));  // max_n: total blocks (flat launch)
+  hipLaunchKernelGGL(sgd_anchor_multi_kernel, dim3((unsigned)max_n), dim3(256), 0, ONDA_STREAM(s), table, n, momentum, weight_decay,
+                     grad_scale, half_lambda);
   return ONDA_LAUNCH_RESULT();
 }
 

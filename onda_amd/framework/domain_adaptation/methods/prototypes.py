@@ -16,7 +16,11 @@ Same classes, methods, arguments, state and log keys as the reference; a differe
   BatchNorm running statistics ride in the tail of the gradient buffer (onda_amd/dist.py): two collectives per step;
 * ``step_sharded`` processes several micro-batches per optimizer step with exactly the arithmetic of that many ranks
   (rank-local batch statistics, averaged gradients, summed prototype statistics, one switch decision): the
-  strong-scaling mode of bench.py and the sequential emulation the multi-rank tests compare against.
+  strong-scaling mode of bench.py and the sequential emulation the multi-rank tests compare against;
+* ``MODEL_REGULARIZATION > 0`` (the EWC penalty towards the static model, reference :81-91, :334-336): the value is one
+  multi-tensor launch per optimizer step and joins the target total detached (``"sym_loss"``, ``"Total target loss"`` and
+  ``"model regularization"`` are the reference's); its gradient never visits ``.grad`` -- the optimizer's launch forms it from
+  the anchors (``ReplaySGD.anchor_of``) with autograd's roundings.  One GPU only.
 """
 from copy import deepcopy
 
@@ -186,9 +190,21 @@ class online_proDA(da_model):
         self.proto_loc, self.proto_cur = f"{snap}/proto_{spec.set_}.pickle", f"{snap}/proto_current.pickle"
         fill = 0 if unset(cfg.TRAINING.PERC_FILL_PER_DOMAIN) else cfg.TRAINING.PERC_FILL_PER_DOMAIN
         self.probability_per_step = fill * 1.0 * cfg.TRAINING.REPLAY_BUFFER / cfg.TRAINING.BATCH_SIZE
-        if not unset(spec.MODEL_REGULARIZATION) and spec.MODEL_REGULARIZATION > 0:
-            raise NotImplementedError("onda_amd: EWC model regularisation is disabled in every shipped config")
         self.model_regularization = None
+        self._step_penalty = None  # inside step_sharded: a list that holds the step's penalty once its first micro-batch has launched it
+        if not unset(spec.MODEL_REGULARIZATION) and spec.MODEL_REGULARIZATION > 0:
+            if odist.is_on():
+                raise NotImplementedError(
+                    "onda_amd: MODEL_REGULARIZATION > 0 with several ranks: the bucketed gradient exchange overlaps the last "
+                    "backward pass, and how the anchored optimizer step interacts with grad_scale across ranks is untested")
+            # the EWC penalty towards the static model (reference :81-91; utils/ewc.py:47-54 with unit Fisher weights): its
+            # value is one multi-tensor launch per step (`model_regularization`), its gradient is formed inside the
+            # optimizer's launch from these anchors -- .grad never holds it
+            half_lambda = spec.MODEL_REGULARIZATION / 2
+            pairs, cache = list(zip(self.static_model.parameters(), self.model.parameters())), {}
+            self.model_regularization = lambda: ops.sqdiff_multi(pairs, half_lambda, cache)
+            self.optimizer.anchor_of = {id(p): p0 for p0, p in pairs}
+            self.optimizer.half_lambda = half_lambda
         self.ece_save = {}
         if isinstance(spec.BN_POLICY, dict):
             self.cfg_spec.BN_POLICY = "freeze"
@@ -426,6 +442,19 @@ class online_proDA(da_model):
                 reg_loss = 0
         else:
             total, ce_loss, rce_loss, reg_loss = ops.seg_losses(out, predictions, w_ce, w_rce, w_reg)
+        penalty = 0
+        if self.model_regularization is not None:
+            # total_loss += ewc_loss(...) (reference :334-336).  The value joins the total detached: its gradient is the
+            # optimizer launch's business (ReplaySGD.anchor_of), backward() has nothing to do for it.  ONE penalty per
+            # optimizer step, however many micro-batches (the weights do not move before optimizer.step()): the first one
+            # launches it here, on the main stream behind the student's forward pass, which has joined the side streams by
+            # now -- 91 + 15 us with the device to itself; ahead of the forward pass it shared the device with the no-grad
+            # passes and sat in the student's chain for 98-400 us, its one-workgroup sum for up to 460 (docs/experiments.md)
+            slot = self._step_penalty if self._step_penalty is not None else []
+            if not slot:
+                slot.append(self.model_regularization())
+            penalty = slot[0]
+            total = total + penalty
         flat = proto_pred["pseudolabels"].reshape(-1)
         return {
             "ce_loss": ce_loss if w_ce > 0 else 0,
@@ -436,7 +465,7 @@ class online_proDA(da_model):
             "regularization_loss": reg_loss if w_reg > 0 else 0,
             "JS Divergance loss": js_loss if w_js > 0 else 0,
             "Total target loss": total,
-            "model regularization": 0,
+            "model regularization": penalty,
         }
 
     def _monitor_log(self, losses):
@@ -765,6 +794,7 @@ class online_proDA(da_model):
             run0 = [b.clone() for b in bufs]
             run_sum = [torch.zeros_like(b) for b in bufs]
         first_log = None
+        self._step_penalty = []  # (filled by the first micro-batch's _target_losses when MODEL_REGULARIZATION is on)
         for i, ((_, batch_target), t) in enumerate(zip(shards, prepared)):
             if run0 is not None:
                 torch._foreach_copy_(bufs, run0)
@@ -784,6 +814,7 @@ class online_proDA(da_model):
             if run0 is not None:
                 torch._foreach_add_(run_sum, bufs)
         self._img_cache = None
+        self._step_penalty = None
         if run0 is not None:
             torch._foreach_mul_(run_sum, scale)
             torch._foreach_copy_(bufs, run_sum)

@@ -1,4 +1,5 @@
-"""Multi-tensor launches over device tables (pinned staging buffers): duplicate-replaying SGD, teacher EMA."""
+"""Multi-tensor launches over device tables (pinned staging buffers): duplicate-replaying SGD (plain and EWC-anchored), teacher
+EMA, the EWC penalty's value."""
 import ctypes
 import os
 from ctypes import byref
@@ -48,18 +49,54 @@ def _table(entries, struct, device):
     return dev
 
 
-def sgd_multi(items, momentum, weight_decay, grad_scale=1.0):
+def sgd_multi(items, momentum, weight_decay, grad_scale=1.0, anchors=None, half_lambda=0.0):
     """items: list of (param, grad, buf, lr, times, fresh).  One launch for all tensors; every gradient element is
-    multiplied by `grad_scale` on the way in."""
+    multiplied by `grad_scale` on the way in.  `anchors` (one tensor or None per item; the EWC penalty of the reference's
+    ewc.py:47-54): the launch adds -2 * (half_lambda * (anchor - param)), rounded as autograd rounds it, to the gradient
+    of the items that have one -- onda_sgd_anchor_multi; an item's grad may be None there (no loss reached it)."""
     blk, ents, first = query("onda_multi_tensor_block"), [], 0
-    for p, g, b, lr, times, fresh in items:
-        ents.append(_lib.OndaSgdEntry(p.data_ptr(), g.data_ptr(), b.data_ptr(), p.numel(), float(lr), int(times), int(fresh), first))
+    for i, (p, g, b, lr, times, fresh) in enumerate(items):
+        head = (p.data_ptr(), g.data_ptr() if g is not None else None, b.data_ptr())
+        tail = (p.numel(), float(lr), int(times), int(fresh), first)
+        if anchors is None:
+            ents.append(_lib.OndaSgdEntry(*head, *tail))
+        else:
+            ents.append(_lib.OndaSgdAnchorEntry(*head, anchors[i].data_ptr() if anchors[i] is not None else None, *tail))
         first += -(-p.numel() // blk)
     dev = items[0][0].device
-    table = _table(ents, _lib.OndaSgdEntry, dev)
-    call("onda_sgd_multi", _p(table), len(ents), float(momentum), float(weight_decay), float(grad_scale), first, _stream())
+    if anchors is None:
+        table = _table(ents, _lib.OndaSgdEntry, dev)
+        call("onda_sgd_multi", _p(table), len(ents), float(momentum), float(weight_decay), float(grad_scale), first, _stream())
+    else:
+        table = _table(ents, _lib.OndaSgdAnchorEntry, dev)
+        call("onda_sgd_anchor_multi", _p(table), len(ents), float(momentum), float(weight_decay), float(grad_scale),
+             float(half_lambda), first, _stream())
     for p, *_ in items:
         torch.autograd.graph.increment_version(p)
+
+
+def sqdiff_multi(pairs, half_lambda, cache=None):
+    """half_lambda * sum over the pairs (a, b) of sum((a - b)^2) as a 0-dim device tensor (float32 differences and
+    squares, a fixed-order sum: onda_sqdiff_multi), one launch for all tensors and one to add its partials up.  `cache`
+    (a dict the caller keeps next to a FIXED list of tensors): table and workspace are rebuilt only when an address
+    changed, as in ema_multi."""
+    key = [(a.data_ptr(), b.data_ptr()) for a, b in pairs]
+    if cache is not None and cache.get("key") == key:
+        table, n, first, ws = cache["table"], cache["n"], cache["blocks"], cache["ws"]
+    else:
+        blk, ents, first = query("onda_multi_tensor_block"), [], 0
+        for a, b in pairs:
+            assert a.numel() == b.numel() and a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
+            ents.append(_lib.OndaSqdiffEntry(a.data_ptr(), b.data_ptr(), a.numel(), first))
+            first += -(-a.numel() // blk)
+        dev = pairs[0][0].device
+        table, n = _table(ents, _lib.OndaSqdiffEntry, dev), len(ents)
+        ws = torch.empty(query("onda_sqdiff_multi_ws", first), dtype=torch.float32, device=dev)
+        if cache is not None:
+            cache.update(key=key, table=table, n=n, blocks=first, ws=ws)
+    result = torch.empty((), dtype=torch.float32, device=ws.device)
+    call("onda_sqdiff_multi", _p(table), n, float(half_lambda), first, _p(ws), _p(result), _stream())
+    return result
 
 
 def ema_multi(items, cache=None):

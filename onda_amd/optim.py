@@ -9,6 +9,11 @@ once per occurrence, sequentially.  ``ReplaySGD`` keeps the same param_groups (s
 and replays ``times`` sequential updates per element inside the kernel.  The first step
 follows torch >= 2 (every occurrence starts a fresh momentum buffer -- what the oracle is
 pinned against, fixture G6).
+
+With ``anchor_of`` (``{id(param): anchor tensor}``) and ``half_lambda`` the launch also applies the EWC penalty
+``half_lambda * sum((anchor - param)^2)`` of the reference's ``utils/ewc.py``: its gradient is formed inside the kernel from
+the parameter value the step finds, with the float32 roundings autograd would have left in ``.grad`` (fixture G20), once per
+element -- every replayed occurrence uses it, as torch's loop uses one ``.grad``.  ``.grad`` itself never holds that term.
 """
 import warnings
 
@@ -18,10 +23,15 @@ from . import ops
 
 
 class ReplaySGD(torch.optim.Optimizer):
-    def __init__(self, params, lr, momentum=0.9, weight_decay=0.0):
+    def __init__(self, params, lr, momentum=0.9, weight_decay=0.0, anchor_of=None, half_lambda=0.0):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")  # "parameter group contains duplicate parameters"
             super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+        # EWC anchors (reference ewc.py:47-54 with unit Fisher weights): {id(param): anchor tensor} and lambda / 2, plain
+        # attributes that may be set later.  The penalty's gradient lambda * (param - anchor) never visits .grad: the launch
+        # forms it from the parameter it reads anyway, once per element, and every replayed occurrence uses it -- what
+        # torch's loop does with the .grad that backward() left
+        self.anchor_of, self.half_lambda = anchor_of, half_lambda
 
     flat_zero = None  # set by the multi-GPU gradient exchange: gradients are views of one flat buffer, zeroed in place
     grad_scale = 1.0  # the next step() multiplies the gradients by this (1 / world after an exchange that left rank SUMS)
@@ -43,15 +53,20 @@ class ReplaySGD(torch.optim.Optimizer):
                     order.append(p)
                 counts[id(p)] += 1
             for p in order:
-                if p.grad is None:
-                    continue
+                anchor = self.anchor_of.get(id(p)) if self.anchor_of else None
+                if p.grad is None and (anchor is None or not p.requires_grad):
+                    continue  # (with an anchor the reference's backward() leaves the penalty's term alone in .grad)
                 st = self.state[p]
                 fresh = "momentum_buffer" not in st
                 if fresh:
                     st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.contiguous_format)
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                g = p.grad if p.grad is None or p.grad.is_contiguous() else p.grad.contiguous()
                 key = (group["momentum"], group["weight_decay"])
-                by_cfg.setdefault(key, []).append((p, g, st["momentum_buffer"], group["lr"], counts[id(p)], fresh))
-        for (momentum, wd), items in by_cfg.items():
-            ops.sgd_multi(items, momentum, wd, self.grad_scale)
+                by_cfg.setdefault(key, []).append(((p, g, st["momentum_buffer"], group["lr"], counts[id(p)], fresh), anchor))
+        for (momentum, wd), entries in by_cfg.items():
+            items = [item for item, _ in entries]
+            if self.anchor_of:
+                ops.sgd_multi(items, momentum, wd, self.grad_scale, [a for _, a in entries], self.half_lambda)
+            else:
+                ops.sgd_multi(items, momentum, wd, self.grad_scale)
         self.grad_scale = 1.0
