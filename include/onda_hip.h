@@ -79,7 +79,7 @@ int onda_conv2d_fwd(const float* x, const float* w, float* y, const float* scale
                     const float* residual, float* stats, float* ws, const OndaConv* c, onda_stream_t s);
 
 /* ---- "f16x2": the same convolution with TWO f16 limbs per operand and a per-tensor power-of-two
- * scale (csrc/conv_h2.hip): a1*b1 + a1*b2 + a2*b1 on v_mfma_f32_16x16x32_f16 at fp32-GEMM accuracy (3e-7 relative
+ * scale (csrc/limbs.h): a1*b1 + a1*b2 + a2*b1 on v_mfma_f32_16x16x32_f16 at fp32-GEMM accuracy (3e-7 relative
  * L2 against fp64).
  * A tensor's scale travels as `amax`: ONDA_AMAX_FLOATS device floats whose maximum is max|x| (producers spread
  * their atomicMax over ONDA_AMAX_SLOTS slots, one cache line apart); every consumer derives 2^e (max * 2^e in
@@ -523,7 +523,7 @@ int onda_resize_nearest_lut(const unsigned char* in, unsigned char* out, int Win
 
 /* library identity, for the loader's sanity check */
 const char* onda_version(void);
-/* factor the second limb of every limb plane is stored with (2048 = 2^11; 1 in measurement builds, csrc/common.h) */
+/* factor the second limb of every limb plane is stored with (2048 = 2^11; 1 in measurement builds, csrc/common.h; used by csrc/limbs.h) */
 float onda_limb2_scale(void);
 
 /* ---- the hybrid switch on the device (csrc/switch.hip) ---------------------------------------------------------------

@@ -7,27 +7,14 @@
 
 #include "onda_hip.h"
 
-// "f16x2" limb planes: the second limb is stored times LIMB2_SCALE (2^11) so that it keeps 11 bits down to 2^-28 of a tensor's
-// maximum; the cross products then carry that factor and live in accumulators of their own.  A measurement build with
-// -DONDA_LIMB2_SCALE=1.f stores it un-scaled (what a single-accumulator kernel would need; DESIGN.md section 7, "Next (0)").
+// "f16x2" limb rows (limbs.h: the format and everything that converts to and from it): the second limb is stored times 2^11.
+// A measurement build with -DONDA_LIMB2_SCALE=1.f stores it un-scaled (what a single-accumulator kernel would need; DESIGN.md
+// section 7, "Next (0)").
 #ifndef ONDA_LIMB2_SCALE
 #define ONDA_LIMB2_SCALE 2048.f
 #endif
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// LIMB ROWS (round 5): how an operand of the pre-split convolutions lies in memory.  Row r -- a pixel of an activation, an
-// output channel of a packed weight -- holds, for every block of 32 channels, the 32 FIRST limbs followed by the 32 SECOND
-// limbs: 128 bytes = one cache line per (row, K-step of 32 channels).  Until round 4 the two limbs were separate planes
-// ([2][rows][ld]); a K-step then fetched two HALF lines per row, and tools/micro/dma_rate.hip shows what that costs: the
-// convolutions' LDS-DMA stream alone (no MFMA, no fragment read) takes as long as the whole 1024 -> 256 1x1 kernel, bound
-// by cache-line REQUESTS per CU, and runs 22-30 % faster with the same bytes as whole lines.
-//   f16 index of (row r, channel c, first limb) = r * 2 * ld + (c / 32) * 64 + c % 32;  second limb: + LIMB2_OFS
-// ld = channels per row (a multiple of 32); a row is 2 * ld f16 = 4 * ld bytes, like an fp32 row.
-constexpr int LIMB2_OFS = 32;
-__host__ __device__ __forceinline__ size_t limb_at(size_t row, int c, int ld) {
-  return row * 2 * (size_t)ld + (size_t)((c >> 5) << 6) + (size_t)(c & 31);
-}
 
 #define ONDA_STREAM(s) (reinterpret_cast<hipStream_t>(s))
 // Argument check at the top of every entry point.  It also drops any stale error another
@@ -99,4 +86,24 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return red[0] + red[1] + red[2] + red[3];
+}
+
+// Multi-tensor launches are FLAT: entry i of a table in device memory owns the workgroups [first_block_i, first_block_{i+1}) of
+// one 1-D grid.  The entry that owns workgroup `block` = the largest i with table[i].first_block <= block, by bisection.  The
+// block starts go to LDS first (one load per thread): ten dependent global loads per workgroup were most of a 16 KB
+// workgroup's life.
+template <class E>
+__device__ __forceinline__ int mt_entry_of(const E* __restrict__ table, int n, int block) {
+  __shared__ int starts[1024];
+  const bool in_lds = n <= 1024;
+  if (in_lds) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) starts[i] = table[i].first_block;
+    __syncthreads();
+  }
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if ((in_lds ? starts[mid] : table[mid].first_block) <= block) lo = mid; else hi = mid - 1;
+  }
+  return lo;
 }

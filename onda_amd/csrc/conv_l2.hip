@@ -3,9 +3,9 @@
 // no ds_write in the K loop (the register-split kernel of conv_h2.hip spends its K-step between two
 // barriers on exactly those, beside the other wave's MFMA stream that starves them).
 //
-// Operand format ("limb rows", the same for activations and weights; common.h limb_at):
+// Operand format ("limb rows", the same for activations and weights; limbs.h):
 //   row r, block of 32 channels b:  [32 x l1][32 x l2] f16,  l1 = f16(x * s),  l2 = f16((x * s - l1) * 2^11),  s = 2^e from max|x|
-// (conv_h2.hip explains the arithmetic): the 128 bytes a K-step needs of a row are ONE cache line (until round 4 the limbs
+// (limbs.h explains the arithmetic): the 128 bytes a K-step needs of a row are ONE cache line (until round 4 the limbs
 // were separate planes, two half lines per row and K-step: the kernels' K loops were bound by line requests per CU,
 // tools/micro/dma_rate.hip).  Activation rows are written by the kernel that produces the tensor (BatchNorm apply /
 // backward, eval-mode conv epilogue, SE gate, the stem's patch kernel) or by split_h2_kernel below from an fp32 tensor
@@ -19,15 +19,12 @@
 // 32 channels, as they lie in memory: one LDS-DMA instruction = 8 rows x 128 B), the 16-byte chunk index XOR-ed with a
 // function of the row (swz8) on the DMA's source side and in the fragment read: conflict-free ds_read_b128.
 #include "conv_common.h"
+#include "limbs.h"
 
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // Order of a 4 x 4 grid of MFMAs: a snake -- row i runs left to right, row i + 1 right to left -- so that consecutive
@@ -35,8 +32,6 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 // fewer operand switches = a slightly higher clock (measured: -1.2 % on the 512 -> 512 3x3 conv, -0.6 % on an ASPP branch,
 // bit-identical results -- every accumulator still sees its K-steps in the same order).
 #define ZZ(i, jj) (((i) & 1) ? 3 - (jj) : (jj))
-
-constexpr float LIMB2_SCALE = ONDA_LIMB2_SCALE, LIMB2_UNSCALE = 1.f / ONDA_LIMB2_SCALE;  // common.h
 
 // Output tiles leave as NON-TEMPORAL (streaming) stores: a convolution never reads its output again, and every round of
 // tiles writes as many bytes as the 4 MB L2 of an XCD holds -- allocated normally they push the weight panel and the
@@ -96,29 +91,6 @@ __device__ __forceinline__ unsigned row_tap_ofs(const RowPos& p, int rr, int ss,
   return ok ? (unsigned)(((p.bH + hi) * c.Wi + wi) * c.ldx) * 4u + chunk16 : 0x80000000u;
 }
 
-struct Scale2 {
-  float s, inv;
-};
-__device__ __forceinline__ Scale2 scale_from(float m);
-__device__ __forceinline__ Scale2 scale_of(const float* __restrict__ amax) { return scale_from(amax_read(amax)); }
-__device__ __forceinline__ Scale2 scale_from(const float m) {
-  int e = 0;
-  if (m > 0.f && m < 3.0e38f) {
-    int ex;
-    frexpf(m, &ex);  // m = f * 2^ex, f in [0.5, 1)
-    e = 15 - ex;
-    e = e > 100 ? 100 : (e < -100 ? -100 : e);
-  }
-  return Scale2{ldexpf(1.f, e), ldexpf(1.f, -e)};
-}
-
-__device__ __forceinline__ unsigned cvt2h(float lo, float hi) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, f16x2));
-}
-__device__ __forceinline__ f32x2 unpack2h(unsigned p) {
-  return __builtin_convertvector(__builtin_bit_cast(f16x2, p), f32x2);
-}
-
 // x[rows][ldx] fp32 (C valid channels) -> limb rows dst[rows][ldo / 32][2][32] f16 with the scale of *amax
 __global__ __launch_bounds__(256) void split_h2_kernel(const float* __restrict__ x, long long rows, int C, int ldx,
                                                        _Float16* __restrict__ dst, int ldo, long long plane,
@@ -132,14 +104,7 @@ __global__ __launch_bounds__(256) void split_h2_kernel(const float* __restrict__
     const f32x4 v0 = *reinterpret_cast<const f32x4*>(x + row * ldx + ch) * s;
     const f32x4 v1 = *reinterpret_cast<const f32x4*>(x + row * ldx + ch + 4) * s;
     u32x4 l1, l2;
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-      const float a = h < 2 ? v0[2 * h] : v1[2 * h - 4], b = h < 2 ? v0[2 * h + 1] : v1[2 * h - 3];
-      const unsigned p = cvt2h(a, b);
-      const f32x2 f = unpack2h(p);
-      l1[h] = p;
-      l2[h] = cvt2h((a - f[0]) * LIMB2_SCALE, (b - f[1]) * LIMB2_SCALE);
-    }
+    split8(v0, v1, l1, l2);
     _Float16* o = dst + limb_at((size_t)row, ch, ldo);
     *reinterpret_cast<u32x4*>(o) = l1;
     *reinterpret_cast<u32x4*>(o + LIMB2_OFS) = l2;
@@ -177,10 +142,9 @@ __global__ __launch_bounds__(256) void stem_im2col_l2_kernel(const float* __rest
     u32x4 l1, l2;
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
-      const unsigned pk = cvt2h(v[2 * h], v[2 * h + 1]);
-      const f32x2 f = unpack2h(pk);
-      l1[h] = pk;
-      l2[h] = cvt2h((v[2 * h] - f[0]) * LIMB2_SCALE, (v[2 * h + 1] - f[1]) * LIMB2_SCALE);
+      const LimbPair p = split2(v[2 * h], v[2 * h + 1]);
+      l1[h] = p.l1;
+      l2[h] = p.l2;
     }
     _Float16* o = dst + limb_at((size_t)m, k0, Kp);
     *reinterpret_cast<u32x4*>(o) = l1;
@@ -473,27 +437,17 @@ __device__ __forceinline__ void l2_epilogue_limbs(const ConvK& a, const f32x4 (&
       const bool live = m < a.M && vn;
       v = v * sc + sh;
       if (a.resl != nullptr) {
+        const f32x4 j = join4(r1[i][r], r2[i][r]);
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const f32x2 p1 = unpack2h(r1[i][r][h]), p2 = unpack2h(r2[i][r][h]);
-          v[2 * h] += (p1[0] + p2[0] * LIMB2_UNSCALE) * ri;
-          v[2 * h + 1] += (p1[1] + p2[1] * LIMB2_UNSCALE) * ri;
-        }
+        for (int q = 0; q < 4; ++q) v[q] += j[q] * ri;
       }
       if (c.relu) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.f);
       }
       if (live) mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
-      const f32x4 w = v * so;
       u32x2 l1, l2;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const unsigned pk = cvt2h(w[2 * h], w[2 * h + 1]);
-        const f32x2 f = unpack2h(pk);
-        l1[h] = pk;
-        l2[h] = cvt2h((w[2 * h] - f[0]) * LIMB2_SCALE, (w[2 * h + 1] - f[1]) * LIMB2_SCALE);
-      }
+      split4(v * so, l1, l2);
       if constexpr (COUNTED) {
 #if defined(__HIP_DEVICE_COMPILE__)
         const unsigned off = vn ? (unsigned)(limb_at((size_t)(m - m0), n, c.ldy) * 2) : OOB;  // rows past M: past the buffer's end
@@ -1569,26 +1523,20 @@ __global__ __launch_bounds__(256) void conv_l2_fixup_kernel(const ConvK a, int G
       if (a.resl != nullptr) {
         const _Float16* p = a.resl + limb_at((size_t)m, n, c.ldr);
         const u32x2 q1 = *reinterpret_cast<const u32x2*>(p), q2 = *reinterpret_cast<const u32x2*>(p + LIMB2_OFS);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const f32x2 p1 = unpack2h(q1[h]), p2 = unpack2h(q2[h]);
-          o[2 * h] += (p1[0] + p2[0] * LIMB2_UNSCALE) * ri;
-          o[2 * h + 1] += (p1[1] + p2[1] * LIMB2_UNSCALE) * ri;
-        }
+        o += join4(q1, q2) * ri;
       }
       if (c.relu) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = fmaxf(o[j], 0.f);
       }
       mx = fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3])));
-      const f32x4 w = o * so;
       u32x2 l1, l2;
+      const f32x4 w = o * so;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        const unsigned pk = cvt2h(w[2 * h], w[2 * h + 1]);
-        const f32x2 f = unpack2h(pk);
-        l1[h] = pk;
-        l2[h] = cvt2h((w[2 * h] - f[0]) * LIMB2_SCALE, (w[2 * h + 1] - f[1]) * LIMB2_SCALE);
+        const LimbPair p = split2(w[2 * h], w[2 * h + 1]);
+        l1[h] = p.l1;
+        l2[h] = p.l2;
       }
       _Float16* dst = a.yl + limb_at((size_t)m, n, c.ldy);
       *reinterpret_cast<u32x2*>(dst) = l1;
@@ -1662,10 +1610,9 @@ __global__ __launch_bounds__(256) void conv_l2_fixup_kernel(const ConvK a, int G
 // before each group of reads (it cannot tell the stage being read from the stages being filled), which serialises the
 // ring.  In assembly nothing is waited for automatically: lds_wait() below is the s_waitcnt lgkmcnt(0) for them, tied to
 // the destination registers so that no MFMA that uses them can be scheduled above it.
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 template <int OFS = 0>  // (byte offset in the instruction's immediate field: the second limbs lie 256 bytes behind the first)
 __device__ __forceinline__ f16x8 tr_read8(unsigned a0, unsigned a1) {
-  u32x2_t lo, hi;
+  u32x2 lo, hi;
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(a0), "n"(OFS));
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(a1), "n"(OFS));
   const u32x4 r = {lo[0], lo[1], hi[0], hi[1]};

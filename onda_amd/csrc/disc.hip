@@ -31,44 +31,14 @@
 //               line come from the same workgroup a few iterations apart (L2 merges them);
 //   backward -- one thread per (b, y, c, x), x fastest: 4-byte stores that cover a plane's row contiguously; the loads walk one
 //               S row pair per image row (2 * Ws * Cp * 4 bytes, read by all C channels in turn: it stays in L2).
-#include "common.h"
+#include "limbs.h"
 
 namespace {
 
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned cvt2h(float lo, float hi) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, f16x2));
-}
-__device__ __forceinline__ f32x2 unpack2h(unsigned p) {
-  return __builtin_convertvector(__builtin_bit_cast(f16x2, p), f32x2);
-}
-
-// 2^e with max * 2^e in [2^14, 2^15) (conv_h2.hip, scale_of: every producer and consumer of a limb tensor derives it alike)
-__device__ __forceinline__ float limb_scale(const float* __restrict__ amax) {
-  const float m = amax_read(amax);
-  int e = 0;
-  if (m > 0.f && m < 3.0e38f) {
-    int ex;
-    frexpf(m, &ex);
-    e = 15 - ex;
-    e = e > 100 ? 100 : (e < -100 ? -100 : e);
-  }
-  return ldexpf(1.f, e);
-}
-
 // 8 scaled values -> 8 first limbs at o, 8 second limbs LIMB2_OFS further
-__device__ __forceinline__ void store_limbs8(_Float16* o, const float* v) {
+__device__ __forceinline__ void store_limbs8(_Float16* o, const float (&v)[8]) {
   u32x4 l1, l2;
-#pragma unroll
-  for (int h = 0; h < 4; ++h) {
-    const unsigned p = cvt2h(v[2 * h], v[2 * h + 1]);
-    const f32x2 f = unpack2h(p);
-    l1[h] = p;
-    l2[h] = cvt2h((v[2 * h] - f[0]) * ONDA_LIMB2_SCALE, (v[2 * h + 1] - f[1]) * ONDA_LIMB2_SCALE);
-  }
+  split8(v, l1, l2);
   *reinterpret_cast<u32x4*>(o) = l1;
   *reinterpret_cast<u32x4*>(o + LIMB2_OFS) = l2;
 }
@@ -81,7 +51,7 @@ struct DiscGeom {
 template <bool NCHW>
 __global__ __launch_bounds__(256) void s2d_split_kernel(const float* __restrict__ x, DiscGeom g, const float* __restrict__ amax,
                                                         _Float16* __restrict__ dst) {
-  const float s = limb_scale(amax);
+  const float s = scale_of(amax).s;
   const int c8 = g.Cp >> 3, C4 = 4 * g.C;
   const long long n = (long long)g.B * g.Hs * g.Ws * c8;
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
@@ -133,7 +103,7 @@ __global__ __launch_bounds__(256) void s2d_split_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void d2s_bwd_nhwc_kernel(const float* __restrict__ gs, const float* __restrict__ gamax,
                                                            const float* __restrict__ x, DiscGeom g, _Float16* __restrict__ dl,
                                                            float* __restrict__ df) {
-  const float s = dl != nullptr ? limb_scale(gamax) : 1.f;
+  const float s = dl != nullptr ? scale_of(gamax).s : 1.f;
   const int c8 = g.C >> 3;
   const long long n = (long long)g.B * g.H * g.W * c8;
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {

@@ -746,26 +746,8 @@ __global__ void proto_append_counter_kernel(float* __restrict__ counter, const f
 
 // ---- multi-tensor optimizer / teacher ---------------------------------------------------------
 // FLAT launches (see pack_h2_multi_kernel): an entry owns the blocks [first_block, first_block + ceil(n / MT_BLOCK)) of a 1-D
-// grid and is found by bisection -- a (largest tensor) x (217 tensors) grid is nine tenths empty workgroups.
+// grid and is found by bisection (common.h mt_entry_of) -- a (largest tensor) x (217 tensors) grid is nine tenths empty workgroups.
 constexpr int MT_BLOCK = 4096;  // elements per workgroup: four 16-byte vectors per thread
-template <class E>
-__device__ __forceinline__ int mt_entry_of(const E* __restrict__ table, int n, int block) {
-  // the block starts go to LDS first (one load per thread): ten dependent global loads per workgroup were most of a
-  // 16 KB workgroup's life
-  __shared__ int starts[1024];
-  const bool in_lds = n <= 1024;
-  if (in_lds) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) starts[i] = table[i].first_block;
-    __syncthreads();
-  }
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if ((in_lds ? starts[mid] : table[mid].first_block) <= block) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 // The entry that owns this workgroup and its element range [i0, i1) of it
 template <class E>
 __device__ __forceinline__ E mt_block(const E* __restrict__ table, int n_entries, int64_t& i0, int64_t& i1) {
@@ -788,38 +770,6 @@ __device__ __forceinline__ void sgd_one(float& p, float& b, float g, float lr, f
   }
 }
 
-// grad_scale: every gradient element is multiplied by it on the way in (1 / world: the exchanged buffer holds rank SUMS, the
-// division never becomes a pass of its own over 184 MB)
-__global__ __launch_bounds__(256) void sgd_multi_kernel(const OndaSgdEntry* __restrict__ table, int n_entries, float momentum,
-                                                        float wd, float grad_scale) {
-  int64_t i0, i1;
-  const OndaSgdEntry e = mt_block(table, n_entries, i0, i1);
-  if (mt_vector_block(i0, i1, e.p, e.g, e.buf)) {
-#pragma unroll
-    for (int k = 0; k < MT_BLOCK / 1024; ++k) {
-      const int64_t i = i0 + (k * 256 + threadIdx.x) * 4;
-      f32x4 p = *reinterpret_cast<const f32x4*>(e.p + i), b = e.fresh ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(e.buf + i);
-      const f32x4 g = *reinterpret_cast<const f32x4*>(e.g + i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float pj = p[j], bj = b[j];
-        sgd_one(pj, bj, g[j] * grad_scale, e.lr, momentum, wd, e.times, e.fresh);
-        p[j] = pj;
-        b[j] = bj;
-      }
-      *reinterpret_cast<f32x4*>(e.p + i) = p;
-      *reinterpret_cast<f32x4*>(e.buf + i) = b;
-    }
-    return;
-  }
-  for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
-    float p = e.p[i], b = e.fresh ? 0.f : e.buf[i];
-    sgd_one(p, b, e.g[i] * grad_scale, e.lr, momentum, wd, e.times, e.fresh);
-    e.p[i] = p;
-    e.buf[i] = b;
-  }
-}
-
 // ---- EWC anchor (utils/ewc.py:47-54 with unit Fisher weights; prototypes.py:334-336) ----------------------------------------
 // The penalty's gradient, as autograd leaves it in .grad under upstream 1, added to the scaled gradient: three roundings and
 // one more for the sum, none of them fused (a fused multiply-add would skip the rounding of the product that ATen's
@@ -833,19 +783,23 @@ __device__ __forceinline__ float anchored_grad(float g, float grad_scale, float 
   return gs + c;
 }
 
-// One block of one entry.  ANCHORED = false is sgd_multi_kernel's body, expression for expression: an entry without an anchor
-// takes it, so that it is updated with the bits onda_sgd_multi gives it.
-template <bool ANCHORED>
-__device__ __forceinline__ void sgd_anchor_block(const OndaSgdAnchorEntry& e, int64_t i0, int64_t i1, float momentum, float wd,
-                                                 float grad_scale, float half_lambda) {
-  if (mt_vector_block(i0, i1, e.p, e.g, e.buf) && (!ANCHORED || (reinterpret_cast<size_t>(e.anchor) & 15) == 0)) {
+// One block of one entry, for both optimizer launches: an OndaSgdEntry, and an OndaSgdAnchorEntry without an anchor, take
+// ANCHORED = false -- one expression, so the anchored launch updates an un-anchored entry with the bits onda_sgd_multi gives it.
+// grad_scale: every gradient element is multiplied by it on the way in (1 / world: the exchanged buffer holds rank SUMS, the
+// division never becomes a pass of its own over 184 MB)
+template <bool ANCHORED, class Entry>
+__device__ __forceinline__ void sgd_block(const Entry& e, int64_t i0, int64_t i1, float momentum, float wd, float grad_scale,
+                                          float half_lambda) {
+  bool vec = mt_vector_block(i0, i1, e.p, e.g, e.buf);
+  if constexpr (ANCHORED) vec = vec && (reinterpret_cast<size_t>(e.anchor) & 15) == 0;
+  if (vec) {
 #pragma unroll
     for (int k = 0; k < MT_BLOCK / 1024; ++k) {
       const int64_t i = i0 + (k * 256 + threadIdx.x) * 4;
       f32x4 p = *reinterpret_cast<const f32x4*>(e.p + i), b = e.fresh ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(e.buf + i);
       const f32x4 g = !ANCHORED || e.g ? *reinterpret_cast<const f32x4*>(e.g + i) : f32x4{0.f, 0.f, 0.f, 0.f};
       f32x4 a = {0.f, 0.f, 0.f, 0.f};
-      if (ANCHORED) a = *reinterpret_cast<const f32x4*>(e.anchor + i);
+      if constexpr (ANCHORED) a = *reinterpret_cast<const f32x4*>(e.anchor + i);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float pj = p[j], bj = b[j];
@@ -863,7 +817,7 @@ __device__ __forceinline__ void sgd_anchor_block(const OndaSgdAnchorEntry& e, in
   }
   for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
     float p = e.p[i], b = e.fresh ? 0.f : e.buf[i];
-    if (ANCHORED)
+    if constexpr (ANCHORED)
       sgd_one(p, b, anchored_grad(e.g ? e.g[i] : 0.f, grad_scale, half_lambda, e.anchor[i], p), e.lr, momentum, wd, e.times, e.fresh);
     else
       sgd_one(p, b, e.g[i] * grad_scale, e.lr, momentum, wd, e.times, e.fresh);
@@ -872,14 +826,21 @@ __device__ __forceinline__ void sgd_anchor_block(const OndaSgdAnchorEntry& e, in
   }
 }
 
+__global__ __launch_bounds__(256) void sgd_multi_kernel(const OndaSgdEntry* __restrict__ table, int n_entries, float momentum,
+                                                        float wd, float grad_scale) {
+  int64_t i0, i1;
+  const OndaSgdEntry e = mt_block(table, n_entries, i0, i1);
+  sgd_block<false>(e, i0, i1, momentum, wd, grad_scale, 0.f);
+}
+
 __global__ __launch_bounds__(256) void sgd_anchor_multi_kernel(const OndaSgdAnchorEntry* __restrict__ table, int n_entries,
                                                                float momentum, float wd, float grad_scale, float half_lambda) {
   int64_t i0, i1;
   const OndaSgdAnchorEntry e = mt_block(table, n_entries, i0, i1);
   if (e.anchor)
-    sgd_anchor_block<true>(e, i0, i1, momentum, wd, grad_scale, half_lambda);
+    sgd_block<true>(e, i0, i1, momentum, wd, grad_scale, half_lambda);
   else
-    sgd_anchor_block<false>(e, i0, i1, momentum, wd, grad_scale, half_lambda);
+    sgd_block<false>(e, i0, i1, momentum, wd, grad_scale, half_lambda);
 }
 
 // The penalty's value: one float32 partial per workgroup (differences and squares in float32, as the reference has them) ...

@@ -1,5 +1,5 @@
 // BatchNorm around the pre-split convolutions (conv_l2.hip): the kernels that PRODUCE a conv operand write it
-// as limb rows (out[M][C / 32][2][32] f16: common.h limb_at; 4 bytes per element like fp32) instead of fp32 + a later
+// as limb rows (out[M][C / 32][2][32] f16: limbs.h; 4 bytes per element like fp32) instead of fp32 + a later
 // split pass.  ("limb planes" below: the same two limbs, which lay in two planes until round 4.)
 //
 // A limb plane needs its tensor's power-of-two scale BEFORE the first element is written, i.e. an upper bound
@@ -11,64 +11,10 @@
 //             |dx| <= |gamma*invstd| * (max|g| + |mean g| + max|xhat| * |mean g*xhat|) per channel; max|g| comes
 //             out of the reduction pass that already reads every element.
 // A bound instead of the maximum costs precision only at the far small end of a tensor (a bound 2^k too large:
-// full two-limb accuracy down to 2^-(28-k) of the maximum instead of 2^-28; conv_h2.hip).
-#include "common.h"
+// full two-limb accuracy down to 2^-(28-k) of the maximum instead of 2^-28; limbs.h).
+#include "limbs.h"
 
 namespace {
-
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr float LIMB2_SCALE = ONDA_LIMB2_SCALE, LIMB2_UNSCALE = 1.f / ONDA_LIMB2_SCALE;  // common.h
-
-struct Scale2 {
-  float s, inv;
-};
-__device__ __forceinline__ Scale2 scale_of(const float* __restrict__ amax) {
-  const float m = amax_read(amax);
-  int e = 0;
-  if (m > 0.f && m < 3.0e38f) {
-    int ex;
-    frexpf(m, &ex);
-    e = 15 - ex;
-    e = e > 100 ? 100 : (e < -100 ? -100 : e);
-  }
-  return Scale2{ldexpf(1.f, e), ldexpf(1.f, -e)};
-}
-__device__ __forceinline__ unsigned cvt2h(float lo, float hi) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, f16x2));
-}
-__device__ __forceinline__ f32x2 unpack2h(unsigned p) {
-  return __builtin_convertvector(__builtin_bit_cast(f16x2, p), f32x2);
-}
-// 8 scaled floats -> 8 + 8 f16 (16 bytes per limb)
-__device__ __forceinline__ void split8(const f32x4 v0, const f32x4 v1, u32x4& l1, u32x4& l2) {
-#pragma unroll
-  for (int h = 0; h < 4; ++h) {
-    const float a = h < 2 ? v0[2 * h] : v1[2 * h - 4], b = h < 2 ? v0[2 * h + 1] : v1[2 * h - 3];
-    const unsigned p = cvt2h(a, b);
-    const f32x2 f = unpack2h(p);
-    l1[h] = p;
-    l2[h] = cvt2h((a - f[0]) * LIMB2_SCALE, (b - f[1]) * LIMB2_SCALE);
-  }
-}
-// 8 + 8 f16 -> 8 floats (still scaled)
-__device__ __forceinline__ void join8(const u32x4 l1, const u32x4 l2, f32x4& v0, f32x4& v1) {
-#pragma unroll
-  for (int h = 0; h < 4; ++h) {
-    const f32x2 a = unpack2h(l1[h]), b = unpack2h(l2[h]);
-    const float x0 = a[0] + b[0] * LIMB2_UNSCALE, x1 = a[1] + b[1] * LIMB2_UNSCALE;
-    if (h < 2) {
-      v0[2 * h] = x0;
-      v0[2 * h + 1] = x1;
-    } else {
-      v1[2 * h - 4] = x0;
-      v1[2 * h - 3] = x1;
-    }
-  }
-}
 
 #define LD4(p) (*reinterpret_cast<const f32x4*>(p))
 

@@ -1,6 +1,6 @@
 // HBM-bound pointwise / stencil kernels of the hot path: ceil-mode max-pool, the SE gate,
 // channel scaling, align_corners bilinear upsampling (plain, gradient, fused argmax / cross-entropy / calibration / entropy map).
-#include "common.h"
+#include "limbs.h"
 #include <type_traits>
 
 namespace {
@@ -10,25 +10,13 @@ namespace {
 // ---- MaxPool 3x3 / s2 / p1 / ceil_mode, NHWC -------------------------------------------
 // yl != nullptr: the result goes out as LIMB ROWS (the operand format of the convolutions that read it, conv_l2.hip; scale from
 // `amax` = max|x|: a maximum over windows of x cannot pass it) instead of fp32 -- no fp32 copy, no split pass behind the pool
-typedef _Float16 mp_f16x2 __attribute__((ext_vector_type(2)));
-typedef float mp_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned mp_u32x2 __attribute__((ext_vector_type(2)));
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                           uint8_t* __restrict__ idx, int B, int Hi, int Wi, int C,
                                                           int Ho, int Wo, _Float16* __restrict__ yl,
                                                           const float* __restrict__ amax) {
   const int c4 = C / 4;
   float so = 1.f;
-  if (yl != nullptr) {  // 2^e with max|x| * 2^e in [2^14, 2^15) (conv_h2.hip)
-    const float m = amax_read(amax);
-    int ex = 0;
-    if (m > 0.f && m < 3.0e38f) {
-      frexpf(m, &ex);
-      ex = 15 - ex;
-      ex = ex > 100 ? 100 : (ex < -100 ? -100 : ex);
-    }
-    so = ldexpf(1.f, ex);
-  }
+  if (yl != nullptr) so = scale_of(amax).s;
   const size_t total = (size_t)B * Ho * Wo * c4;
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
     const int col = (int)(e % c4) * 4;
@@ -58,18 +46,17 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restric
       }
     }
     if (yl != nullptr) {
+      u32x2 l1, l2;
       const f32x4 w = best * so;
-      mp_u32x2 l1, l2;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        const mp_f16x2 p = __builtin_convertvector(mp_f32x2{w[2 * h], w[2 * h + 1]}, mp_f16x2);
-        const mp_f32x2 f = __builtin_convertvector(p, mp_f32x2);
-        l1[h] = __builtin_bit_cast(unsigned, p);
-        l2[h] = __builtin_bit_cast(unsigned, __builtin_convertvector(mp_f32x2{(w[2 * h] - f[0]) * ONDA_LIMB2_SCALE, (w[2 * h + 1] - f[1]) * ONDA_LIMB2_SCALE}, mp_f16x2));
+        const LimbPair p = split2(w[2 * h], w[2 * h + 1]);
+        l1[h] = p.l1;
+        l2[h] = p.l2;
       }
       _Float16* o = yl + limb_at(e / c4, col, C);
-      *reinterpret_cast<mp_u32x2*>(o) = l1;
-      *reinterpret_cast<mp_u32x2*>(o + LIMB2_OFS) = l2;
+      *reinterpret_cast<u32x2*>(o) = l1;
+      *reinterpret_cast<u32x2*>(o + LIMB2_OFS) = l2;
     } else {
       *reinterpret_cast<f32x4*>(y + e * 4) = best;
     }

@@ -12,7 +12,7 @@ STEM_K = 160   # 7*7*3 = 147 patch values padded to a multiple of 32
 # How the convolutions (forward, data gradient, weight gradient) are evaluated:
 #   "f16x2" : fp32 operands scaled by a per-tensor power of two and split into two f16 limbs, three
 #             products on the f16 MFMA pipe with fp32 accumulation (the accuracy of an fp32 FMA chain at
-#             16/3 of the fp32-MFMA rate; csrc/conv_l2.hip; the arithmetic is described in conv_h2.hip) -- the default;
+#             16/3 of the fp32-MFMA rate; csrc/conv_l2.hip; the arithmetic is described in limbs.h) -- the default;
 #   "f32"   : v_mfma_f32_32x32x2_f32 (an exact fp32 fmaf chain; csrc/conv.hip) -- the strict-fp32 leg of bench.py and the
 #             yardstick of test_f16x2_steps_track_the_exact_f32_steps; also what a conv whose weight the f16x2 packers do not
 #             take (element count not a multiple of 4) runs on.

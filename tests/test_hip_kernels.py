@@ -1125,7 +1125,7 @@ def test_bad_arguments_raise():
 
 
 def test_limb_row_strides_must_be_whole_32_channel_blocks():
-    """Limb rows hold [32 x l1][32 x l2] per block of 32 channels (common.h limb_at): a row stride of 40 would put channels
+    """Limb rows hold [32 x l1][32 x l2] per block of 32 channels (limbs.h limb_at): a row stride of 40 would put channels
     32..39 into the next row (and past the buffer on the last one).  The two public producers of limb rows refuse it
     (round-5 advisor: they still validated the two-plane contract, % 8)."""
     from onda_amd import ops
