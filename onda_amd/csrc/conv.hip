@@ -47,28 +47,23 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 2) void conv_fwd_kernel(con
 
   // XCD-aware order: blocks b and b+8 share an XCD (round-robin dispatch); give each XCD a
   // contiguous run of tiles (or of the unit space); N-tiles of one M-tile are adjacent in it.
-  const int nblk = gridDim.x, bid = blockIdx.x;
-  const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-  const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int nblk = gridDim.x, bid = blockIdx.x, swz = xcd_band(bid, nblk);
   const int KT = a.taps * a.kcper;
   // SK: a.tiles_dp tiles (whole rounds of the grid) are processed one per workgroup, all starting
   // at k = 0 together -- workgroups of an XCD then stream the SAME weight slices at the same time,
   // which is what keeps them in its L2.  Only the remaining (< gridDim.x) tiles are cut into
-  // equal unit ranges over all workgroups.
+  // equal unit ranges over all workgroups (StreamK, conv_common.h).
   const int tiles_all = a.tilesM * a.tilesN;
-  const int tiles_dp = SK ? a.tiles_dp : tiles_all;
-  const long long U = (long long)(tiles_all - tiles_dp) * KT;  // units of the stream-K remainder
-  long long u = SK ? swz * U / nblk : 0;
+  const StreamK sk(tiles_all, SK ? a.tiles_dp : tiles_all, KT, nblk);
+  long long u = SK ? sk.begin(swz) : 0;
   const long long u_begin = u;
-  const long long u_end = SK ? (swz + 1) * U / nblk : 0;
+  const long long u_end = SK ? sk.begin(swz + 1) : 0;
   int dp_tile = swz;  // next data-parallel tile of this workgroup
   const int ccol = (t & 7) * 4, rbase = t >> 3;
 
-  while (dp_tile < tiles_dp || u < u_end) {
-  const bool dp = dp_tile < tiles_dp;
-  const int tile = dp ? dp_tile : tiles_dp + (int)(u / KT);
-  const int k_begin = dp ? 0 : (int)(u - (long long)(tile - tiles_dp) * KT);
-  const int k_end = dp ? KT : (int)min((long long)KT, k_begin + (u_end - u));
+  while (sk.valid(dp_tile, u, u_end)) {
+  const SkItem it = sk.item(dp_tile, u, u_end);
+  const int tile = it.tile, k_begin = it.k_begin, k_end = it.k_end;
   const int tile_n = tile % a.tilesN, tile_m = tile / a.tilesN;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -172,10 +167,10 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, 2) void conv_fwd_kernel(con
     __syncthreads();
   }
 
-  if (dp) dp_tile += nblk; else u += k_end - k_begin;
+  if (it.dp) dp_tile += sk.G; else u += k_end - k_begin;  // (StreamK::advance, written out: the call changes this kernel's code)
   if (SK && (k_begin != 0 || k_end != KT)) {
-    // partial tile: raw accumulators to this block's slot (0 = its first segment, 1 = its last)
-    float* slot = a.ws + ((size_t)swz * 2 + (u - (k_end - k_begin) == u_begin ? 0 : 1)) * (BM * BN);
+    // partial tile: raw accumulators to this block's slot
+    float* slot = StreamK::piece_of<BM * BN>(a.ws, swz, u - (k_end - k_begin), u_begin);
     conv_store_partial<BN, TM, TN>(slot, acc, wm, wn, lane);
     continue;
   }
@@ -192,18 +187,13 @@ __global__ __launch_bounds__(256) void conv_piece_sum_kernel(const ConvK a, int 
   constexpr int ROWS = 1024 / BN;  // rows per workgroup: 256 threads x float4
   __shared__ int piece[1024];
   const int KT = a.taps * a.kcper;
-  const long long U = (long long)(a.tilesM * a.tilesN - a.tiles_dp) * KT;
+  const StreamK sk(a.tilesM * a.tilesN, a.tiles_dp, KT, G);
   const int lt = blockIdx.x;  // remainder-local tile
-  const long long t0 = (long long)lt * KT, t1 = t0 + KT;
-  const int vs = (int)(((t0 + 1) * G + U - 1) / U - 1), ve = (int)((t1 * G + U - 1) / U - 1);
+  const SkTile tu = sk.tile_units(lt);
+  const int vs = sk.first_wg(tu), ve = sk.last_wg(tu);
   if (vs == ve) return;
   const int t = threadIdx.x, npieces = ve - vs + 1;
-  for (int p = t; p < npieces; p += 256) {
-    const int vb = vs + p;
-    const long long b0 = (long long)vb * U / G, b1 = (long long)(vb + 1) * U / G;
-    const long long g0 = max(b0, t0), g1 = min(b1, t1);
-    piece[p] = g1 > g0 ? vb * 2 + (g0 == b0 ? 0 : 1) : -1;
-  }
+  for (int p = t; p < npieces; p += 256) piece[p] = sk.piece(vs + p, tu);
   __syncthreads();
   const int eo = (blockIdx.y * ROWS) * BN + t * 4;
   f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -223,10 +213,10 @@ __global__ __launch_bounds__(256) void conv_fixup_kernel(const ConvK a, int G, c
   __shared__ f32x4 red[2][256];
   const OndaConv& c = a.c;
   const int KT = a.taps * a.kcper;
-  const long long U = (long long)(a.tilesM * a.tilesN - a.tiles_dp) * KT;  // the stream-K remainder
+  const StreamK sk(a.tilesM * a.tilesN, a.tiles_dp, KT, G);
   const int tile = a.tiles_dp + blockIdx.x;
-  const long long t0 = (long long)blockIdx.x * KT, t1 = t0 + KT;
-  const int vs = (int)(((t0 + 1) * G + U - 1) / U - 1), ve = (int)((t1 * G + U - 1) / U - 1);
+  const SkTile tu = sk.tile_units(blockIdx.x);
+  const int vs = sk.first_wg(tu), ve = sk.last_wg(tu);
   if (vs == ve) return;  // computed whole by one workgroup: its own epilogue already ran
   const int tile_n = tile % a.tilesN, tile_m = tile / a.tilesN;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
@@ -241,12 +231,7 @@ __global__ __launch_bounds__(256) void conv_fixup_kernel(const ConvK a, int G, c
   // contributing workgroups (ascending = the fixed summation order) and the slot each used
   __shared__ int piece[1024];
   const int npieces = ve - vs + 1;  // <= gridDim of the conv kernel <= 1024 (checked on the host)
-  for (int p = t; p < npieces; p += 256) {
-    const int vb = vs + p;
-    const long long b0 = (long long)vb * U / G, b1 = (long long)(vb + 1) * U / G;
-    const long long g0 = max(b0, t0), g1 = min(b1, t1);
-    piece[p] = g1 > g0 ? vb * 2 + (g0 == b0 ? 0 : 1) : -1;
-  }
+  for (int p = t; p < npieces; p += 256) piece[p] = sk.piece(vs + p, tu);
   __syncthreads();
 
   f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
@@ -345,11 +330,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradK a) {
   // order, so that the workgroups that stream the same dy rows (all input-channel tiles of a tap and pixel range) and the same
   // x rows find them in ONE L2 instead of eight (as conv_wgrad_l2_kernel does; round 6: this kernel read 3.1 TB/s from the
   // Infinity Cache for operands that eight L2s each fetched for themselves)
-  int bid;
-  {
-    const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = blockIdx.x & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-  }
+  int bid = xcd_band(blockIdx.x, gridDim.x);
   const int tile_c = bid % a.tilesC;
   bid /= a.tilesC;
   const int tap = bid % a.taps;
@@ -714,7 +695,7 @@ int conv_launch_fixup(const ConvK& k, int G, bool wide, hipStream_t st) {
   const int tiles = k.tilesM * k.tilesN - k.tiles_dp;
   if (tiles <= 0) return ONDA_LAUNCH_RESULT();
   // few tiles cut into many pieces: sum the pieces with a wide launch first
-  float* sums = (tiles * 4 < G) ? k.ws + (size_t)G * 2 * 128 * 128 : nullptr;
+  float* sums = (tiles * 4 < G) ? k.ws + StreamK::ws_floats(G, 128 * 128) : nullptr;
   if (wide) {
     if (sums) hipLaunchKernelGGL((conv_piece_sum_kernel<128, 128>), dim3(tiles, 128 * 128 / 1024), dim3(256), 0, st, k, G, sums);
     hipLaunchKernelGGL((conv_fixup_kernel<128, 128>), dim3(tiles), dim3(256), 0, st, k, G, sums);
@@ -729,7 +710,7 @@ int conv_launch_fixup(const ConvK& k, int G, bool wide, hipStream_t st) {
 int conv_launch_fixup_tile(const ConvK& k, int G, int BM, int BN, hipStream_t st) {
   const int tiles = k.tilesM * k.tilesN - k.tiles_dp;
   if (tiles <= 0) return ONDA_LAUNCH_RESULT();
-  float* sums = (tiles * 4 < G) ? k.ws + (size_t)G * 2 * BM * BN : nullptr;
+  float* sums = (tiles * 4 < G) ? k.ws + StreamK::ws_floats(G, BM * BN) : nullptr;
 #define FIXUP_TILE(BM_, BN_)                                                                                                  \
   do {                                                                                                                        \
     if (sums) hipLaunchKernelGGL((conv_piece_sum_kernel<BM_, BN_>), dim3(tiles, BM_ * BN_ / 1024), dim3(256), 0, st, k, G, sums); \
@@ -764,7 +745,10 @@ int conv_resident_workgroups() {
 
 extern "C" {
 
-int64_t onda_conv_ws_floats(void) { return (int64_t)conv_resident_workgroups() * 3 * 128 * 128; }  // 2 partial slots per workgroup + summed remainder tiles
+int64_t onda_conv_ws_floats(void) {  // the partial slots of every resident workgroup + summed remainder tiles (conv_launch_fixup)
+  const int G = conv_resident_workgroups();
+  return (int64_t)StreamK::ws_floats(G, 128 * 128) + (int64_t)G * 128 * 128;
+}
 
 int onda_conv2d_fwd(const float* x, const float* w, float* y, const float* scale, const float* shift,
                     const float* residual, float* stats, float* ws, const OndaConv* c, onda_stream_t s) {

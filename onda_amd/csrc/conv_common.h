@@ -1,5 +1,6 @@
-// Shared between the fp32 and the split-precision convolution kernels: argument block, the
-// stream-K partial-tile store and the common epilogue (statistics, scale/shift, residual, ReLU,
+// Shared between the fp32 and the split-precision convolution kernels: argument block, the XCD band
+// order of workgroups, the stream-K schedule (StreamK), the stream-K partial-tile store and the
+// common epilogue (statistics, scale/shift, residual, ReLU,
 // slice / scatter store) for a 4-wave workgroup of 32x32 or 16x16 MFMA accumulator tiles.
 #pragma once
 #include "common.h"
@@ -51,6 +52,78 @@ struct WgradK {
 };
 
 constexpr int BK = 32;
+
+// Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share one): the place of block `bid` in an order that
+// hands each XCD a contiguous band of the launch's nblk work items, so that neighbours in that order share an L2.
+template <class B>  // (B: the block index as the kernel holds it, int or unsigned -- the shift below follows it)
+__device__ __forceinline__ int xcd_band(B bid, int nblk) {
+  const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
+// ---- the hybrid stream-K schedule: what its writers (conv_fwd_kernel, conv_l2_kernel, conv_l2x_kernel), its readers
+// (conv_piece_sum_kernel, conv_fixup_kernel, conv_l2_fixup_kernel) and the host's workspace bounds agree on -----------------
+// tiles_dp tiles (whole rounds of the grid) run one per workgroup and round.  The remaining tiles x KT K-steps are U units,
+// cut into G equal contiguous ranges: workgroup w (its place in the XCD band order) has [begin(w), begin(w + 1)).  A range
+// end inside a tile leaves a partial tile in the workspace [G][2][BM * BN]: a range meets at most two tiles in part, its
+// first piece goes to slot 0 of its workgroup, a later one to slot 1.  A writer and a reader that disagree about any line of
+// this give a wrong tile sum, not a crash: keep every one of them here.
+struct SkItem {
+  bool dp;  // a whole tile of the one-per-workgroup rounds
+  int tile, k_begin, k_end;
+};
+struct SkTile {
+  long long t0, t1;  // the units of one remainder tile
+};
+// A workgroup's cursor is (dp_tile, u): its next whole tile, the next unit of its remainder range [begin(w), u_end = begin(w + 1)).
+struct StreamK {
+  // Every member is forced inline, and written so that the kernels' code is what it was with these lines standing in them: a
+  // helper is simplified on its own before it is inlined, so KT is widened ONCE, here, as a kernel does at its first use.
+  int KT, tiles_dp, G;
+  long long U, KTw;
+  __host__ __device__ __forceinline__ StreamK(int tiles_all, int tiles_dp_, int KT_, int G_)
+      : KT(KT_), tiles_dp(tiles_dp_), G(G_), U((long long)(tiles_all - tiles_dp_) * KT_), KTw(KT_) {}
+  __device__ __forceinline__ long long begin(int w) const { return w * U / G; }
+  __device__ __forceinline__ bool valid(const int& dp_tile, const long long& u, const long long& u_end) const { return dp_tile < tiles_dp || u < u_end; }
+  // (selects, as conv_fwd_kernel and conv_l2_kernel had them; conv_l2x_kernel branches once and keeps its own text: experiments.md)
+  __device__ __forceinline__ SkItem item(int dp_tile, long long u, long long u_end) const {
+    const bool dp = dp_tile < tiles_dp;
+    const int tile = dp ? dp_tile : tiles_dp + (int)(u / KTw);
+    const int k_begin = dp ? 0 : (int)(u - (long long)(tile - tiles_dp) * KTw);
+    const int k_end = dp ? KT : (int)min(KTw, k_begin + (u_end - u));
+    return {dp, tile, k_begin, k_end};
+  }
+  __device__ __forceinline__ void advance(int& dp_tile, long long& u, const SkItem& it) const {
+    if (it.dp) dp_tile += G; else u += it.k_end - it.k_begin;
+  }
+  // workspace slot of a piece of workgroup w: 0 for the piece that begins where its range does, 1 for a later one; the slots of G
+  // workgroups end where slot(G, ..) would begin
+  template <class I>
+  __host__ __device__ __forceinline__ static I slot(I w, long long piece_begin, long long range_begin) {
+    return w * 2 + (piece_begin == range_begin ? 0 : 1);
+  }
+  // where a writer stores that piece (TILE = BM * BN floats)
+  template <int TILE>
+  __device__ __forceinline__ static float* piece_of(float* ws, int w, long long piece_begin, long long range_begin) {
+    return ws + slot((size_t)w, piece_begin, range_begin) * TILE;
+  }
+  __host__ __device__ __forceinline__ static size_t ws_floats(int G, int tile_floats) { return slot((size_t)G, 0, 0) * tile_floats; }
+  // readers -- remainder tile lt (0 = tile tiles_dp) and the first and the last workgroup whose range meets its units (equal:
+  // one workgroup computed the tile whole, its own epilogue ran) ...
+  template <class I>  // (int or the unsigned block index: the widening follows it)
+  __device__ __forceinline__ SkTile tile_units(I lt) const {
+    const long long t0 = (long long)lt * KT, t1 = t0 + KT;
+    return {t0, t1};
+  }
+  __device__ __forceinline__ int first_wg(const SkTile& tu) const { return (int)(((tu.t0 + 1) * G + U - 1) / U - 1); }
+  __device__ __forceinline__ int last_wg(const SkTile& tu) const { return (int)((tu.t1 * G + U - 1) / U - 1); }
+  // ... and the slot workgroup w left its piece of that tile in, -1 if its range is empty there
+  __device__ __forceinline__ int piece(int w, const SkTile& tu) const {
+    const long long b0 = begin(w), b1 = begin(w + 1);
+    const long long g0 = max(b0, tu.t0), g1 = min(b1, tu.t1);
+    return g1 > g0 ? slot(w, g0, b0) : -1;
+  }
+};
 
 // Accumulator fragment of one MF x MF MFMA tile: which (row, column) of the tile register e of a
 // lane holds (32x32x* and 16x16x* MFMA result layouts).

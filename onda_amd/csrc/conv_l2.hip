@@ -33,6 +33,50 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 // bit-identical results -- every accumulator still sees its K-steps in the same order).
 #define ZZ(i, jj) (((i) & 1) ? 3 - (jj) : (jj))
 
+// ---- the K-step's arithmetic on a wave's MI x 4 grid of 16 x 16 tiles, written once -------------------------------------
+// (The two that touch the fragment registers are macros beside ZZ, not functions: as functions -- fragments by reference or by
+//  value, the limb picked by the template or by the caller -- they changed the register allocation of the 8-wave kernels.)
+// ACC[i][j] += A x B[j] over the grid in snake order; A: the expression of row i's fragment (af[i][0], a2[i], ...)
+#define MFMA_SNAKE(MI, ACC, A, B)                                                                                       \
+  _Pragma("unroll") for (int i = 0; i < (MI); ++i) _Pragma("unroll") for (int jj = 0; jj < 4; ++jj)                     \
+      ACC[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, B[ZZ(i, jj)], ACC[i][ZZ(i, jj)], 0, 0, 0)
+// the fragments of four 16-row blocks: 16-byte reads 2 048 bytes apart; DST: the expression of block j's register (af[j][0], bf[j])
+#define FRAG_READ4(DST, P) \
+  _Pragma("unroll") for (int j = 0; j < 4; ++j) DST = *reinterpret_cast<const f16x8*>((P) + j * 2048)
+// a1*b1 sums and the cross products (2^11 too large) start at zero ...
+template <int MI>
+__device__ __forceinline__ void acc_clear(f32x4 (&acc)[MI][4], f32x4 (&accx)[MI][4]) {
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[i][j][e] = accx[i][j][e] = 0.f;
+}
+// ... are folded once per tile (the loop over the grid stays at the site: as a helper it changed conv_l2_kernel) ...
+__device__ __forceinline__ f32x4 limb_fold(f32x4 acc, f32x4 accx) { return acc + accx * LIMB2_UNSCALE; }
+// ... and go back to the operands' own units by the two exact factors, one after the other: their product may underflow
+__device__ __forceinline__ f32x4 unscale2(f32x4 v, float ua, float ub) { return (v * ua) * ub; }
+template <int MI>
+__device__ __forceinline__ void acc_unscale(f32x4 (&acc)[MI][4], float ua, float ub) {
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = unscale2(acc[i][j], ua, ub);
+}
+// The epilogues fold the two factors into their per-column constants -- unless the PRODUCT left the normal range (tensors with
+// max|x| around 2^-50 and less): then they are applied to the sums first, as the stream-K pieces do.
+__device__ __forceinline__ bool unscale_folds(float ua, float ub) {
+  const float u = ua * ub;
+  return u >= 0x1p-100f && u <= 0x1p100f;
+}
+template <int MI>
+__device__ __forceinline__ void acc_unscale_unless_folded(f32x4 (&acc)[MI][4], float& ua, float& ub) {
+  if (unscale_folds(ua, ub)) return;
+  acc_unscale(acc, ua, ub);
+  ua = ub = 1.f;
+}
+
 // Output tiles leave as NON-TEMPORAL (streaming) stores: a convolution never reads its output again, and every round of
 // tiles writes as many bytes as the 4 MB L2 of an XCD holds -- allocated normally they push the weight panel and the
 // activation rows the XCD's workgroups share out of it (measured on the short-K 1x1 convolutions: -7..8 % with `nt`).
@@ -482,18 +526,35 @@ __device__ __forceinline__ void l2_epilogue_limbs(const ConvK& a, const f32x4 (&
 }
 
 // ---- forward / data gradient ------------------------------------------------------------------------------------------
+// Tile geometry of the forward kernels: WM x WN waves of 64 x 64 outputs, a ring of STAGES stages of 128-byte rows (both limbs
+// of the K-step's 32 channels), filled in 8-row pieces (1 KiB: one LDS-DMA instruction).
+template <int WM, int WN, int STAGES>
+struct L2Tile {
+  static constexpr int NW = WM * WN;
+  static constexpr int BM = 64 * WM, BN = 64 * WN;
+  static constexpr int A_BYTES = BM * 128, STAGE = A_BYTES + BN * 128, RING = STAGES * STAGE;
+  static constexpr int APW = (BM / 8) / NW, BPW = (BN / 8) / NW;  // pieces per wave and stage
+  static constexpr int DPW = APW + BPW;                            // LDS-DMA instructions per wave per K-step
+  static_assert((BM / 8) % NW == 0 && (BN / 8) % NW == 0 && APW % 2 == 0 && BPW % 2 == 0, "whole 16-row blocks per wave");
+  static_assert(STAGES >= 2, "ring: one stage being read, STAGES - 1 in flight");
+};
+// The ring stage behind `st` (byte offsets):
+template <class T>
+__device__ __forceinline__ int ring_next(int st) { return st + T::STAGE == T::RING ? 0 : st + T::STAGE; }
+// the activation rows' offsets under filter tap tp (the kernels call it through a one-line lambda: called directly it changed them)
+template <int APW>
+__device__ __forceinline__ void tap_offsets(unsigned (&aofs)[APW], const RowPos (&rp)[APW], int tp, const OndaConv& c, const unsigned (&cq)[2]) {
+  const int rr = tp / c.kw, ss = tp - rr * c.kw;
+#pragma unroll
+  for (int d = 0; d < APW; ++d) aofs[d] = row_tap_ofs(rp[d], rr, ss, c, cq[d & 1]);
+}
 template <int WM, int WN, int STAGES, int OCC, bool SK, int DBG = 0>
 __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2_kernel(const ConvK a, unsigned xplane, unsigned wplane, unsigned x_bytes,
                                                                    unsigned w_bytes, const float* __restrict__ xamax,
                                                                    const float* __restrict__ wamax) {
   if (a.c.run_if != nullptr && *a.c.run_if == 0) return;  // predicated launch (onda_switch_step decided on the device)
-  constexpr int NW = WM * WN;
-  constexpr int BM = 64 * WM, BN = 64 * WN;
-  constexpr int A_BYTES = BM * 128, STAGE = A_BYTES + BN * 128;  // 128-byte rows: both limbs of the K-step's 32 channels
-  constexpr int APW = (BM / 8) / NW, BPW = (BN / 8) / NW;        // 8-row pieces (1 KiB: one LDS-DMA instruction) per wave and stage
-  static_assert((BM / 8) % NW == 0 && (BN / 8) % NW == 0 && APW % 2 == 0 && BPW % 2 == 0, "whole 16-row blocks per wave");
-  constexpr int DPW = APW + BPW;  // LDS-DMA instructions per wave per K-step
-  static_assert(STAGES >= 2, "ring: one stage being read, STAGES - 1 in flight");
+  using T = L2Tile<WM, WN, STAGES>;
+  constexpr int NW = T::NW, BM = T::BM, BN = T::BN, A_BYTES = T::A_BYTES, STAGE = T::STAGE, APW = T::APW, BPW = T::BPW, DPW = T::DPW;
   constexpr int AHEAD = STAGES >= 3 ? 2 : 1;     // K-steps in flight beyond the one being read
   constexpr bool STAGGER = NW == 8 && DBG != 6;  // two waves per SIMD: the second half of the workgroup runs half a step late
   static_assert(!STAGGER || STAGES >= 3, "the staggered halves need two steps in flight");
@@ -504,16 +565,13 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2_kernel(const ConvK 
   const int wm = wave / WN, wn = wave % WN;
   const bool late = wave >= NW / 2;
 
-  const int nblk = gridDim.x, bid = blockIdx.x;
-  const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-  const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int nblk = gridDim.x, bid = blockIdx.x, swz = xcd_band(bid, nblk);
   const int KT = a.taps * a.kcper;
   const int tiles_all = a.tilesM * a.tilesN;
-  const int tiles_dp = SK ? a.tiles_dp : tiles_all;
-  const long long U = (long long)(tiles_all - tiles_dp) * KT;
-  long long u = SK ? swz * U / nblk : 0;
+  const StreamK sk(tiles_all, SK ? a.tiles_dp : tiles_all, KT, nblk);
+  long long u = SK ? sk.begin(swz) : 0;
   const long long u_begin = u;
-  const long long u_end = SK ? (swz + 1) * U / nblk : 0;
+  const long long u_end = SK ? sk.begin(swz + 1) : 0;
   int dp_tile = swz;
   const int wstride = a.taps * c.Cin;
   const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.w, w_bytes);
@@ -533,11 +591,10 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2_kernel(const ConvK 
       tk_mark = now;
     }
   };
-  while (dp_tile < tiles_dp || u < u_end) {
-    const bool dp = dp_tile < tiles_dp;
-    const int tile = dp ? dp_tile : tiles_dp + (int)(u / KT);
-    const int k_begin = dp ? 0 : (int)(u - (long long)(tile - tiles_dp) * KT);
-    const int k_end = dp ? KT : (int)min((long long)KT, k_begin + (u_end - u));
+  while (sk.valid(dp_tile, u, u_end)) {
+    const SkItem it = sk.item(dp_tile, u, u_end);
+    const bool dp = it.dp;
+    const int tile = it.tile, k_begin = it.k_begin, k_end = it.k_end;
     const int tile_n = tile % a.tilesN, tile_m = tile / a.tilesN;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -580,11 +637,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2_kernel(const ConvK 
     unsigned aofs[APW];
     int tap_i = dp ? next_live_tap(0) : k_begin / a.kcper;
     int c0_i = dp ? 0 : (k_begin - tap_i * a.kcper) * BK;  // the K-step the next issue() fetches
-    auto set_tap = [&](int tp) {
-      const int rr = tp / c.kw, ss = tp - rr * c.kw;
-#pragma unroll
-      for (int d = 0; d < APW; ++d) aofs[d] = row_tap_ofs(rp[d], rr, ss, c, cq[d & 1]);
-    };
+    auto set_tap = [&](int tp) { tap_offsets(aofs, rp, tp, c, cq); };
     auto issue = [&](int stage_off) {
 #if defined(__HIP_DEVICE_COMPILE__)
       const int sa = c0_i * 4;                       // the row's 128-byte block of channels c0 .. c0 + 31
@@ -611,12 +664,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2_kernel(const ConvK 
     };
 
     f32x4 acc[4][4], accx[4][4];  // a1*b1, and the cross products (2^11 too large)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[i][j][e] = accx[i][j][e] = 0.f;
+    acc_clear(acc, accx);
 
     __syncthreads();  // the previous tile's readers (fragments, epilogue scratch) are done with every LDS region
     set_tap(tap_i);
@@ -639,7 +687,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2_kernel(const ConvK 
     };
     auto issue_next = [&]() {
       issue(st_issue);
-      st_issue = st_issue + STAGE == STAGES * STAGE ? 0 : st_issue + STAGE;
+      st_issue = ring_next<T>(st_issue);
     };
     // fragments: A limbs stay in registers; B limbs stream 2 -> 1 (smaller products first): a1*b2, a2*b1, a1*b1
     f16x8 af[4][2], bf[4], b1[4];
@@ -656,7 +704,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2_kernel(const ConvK 
       Ab2 = lds + st_read + wm * 64 * 128 + fr1;
       Bb = lds + st_read + A_BYTES + wn * 64 * 128 + fr0;
       Bb2 = lds + st_read + A_BYTES + wn * 64 * 128 + fr1;
-      st_read = st_read + STAGE == STAGES * STAGE ? 0 : st_read + STAGE;
+      st_read = ring_next<T>(st_read);
       if constexpr (DBG == 8 || DBG >= 10) return;  // ablation: no fragment reads at all (the MFMAs run on whatever the registers hold)
       if constexpr (DBG == 7) {        // ablation: half of the fragment reads (first limbs only, used for every product)
 #pragma unroll
@@ -665,34 +713,20 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2_kernel(const ConvK 
         for (int j = 0; j < 4; ++j) b1[j] = bf[j] = *reinterpret_cast<const f16x8*>(Bb + j * 2048);
         return;
       }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i][0] = *reinterpret_cast<const f16x8*>(Ab + i * 2048);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i][1] = *reinterpret_cast<const f16x8*>(Ab2 + i * 2048);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const f16x8*>(Bb2 + j * 2048);
+      FRAG_READ4(af[j][0], Ab);
+      FRAG_READ4(af[j][1], Ab2);
+      FRAG_READ4(bf[j], Bb2);
       if constexpr (STAGGER) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b1[j] = *reinterpret_cast<const f16x8*>(Bb + j * 2048);
+        FRAG_READ4(b1[j], Bb);
       }
     };
     auto compute = [&]() {  // "C": 48 MFMAs (one wave per SIMD: the b1 fragments are fetched behind the first 16)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) accx[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][0], bf[ZZ(i, jj)], accx[i][ZZ(i, jj)], 0, 0, 0);
+      MFMA_SNAKE(4, accx, af[i][0], bf);
       if constexpr (!STAGGER && DBG != 7 && DBG != 8 && DBG < 10) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b1[j] = *reinterpret_cast<const f16x8*>(Bb + j * 2048);
+        FRAG_READ4(b1[j], Bb);
       }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) accx[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][1], b1[ZZ(i, jj)], accx[i][ZZ(i, jj)], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) acc[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][0], b1[ZZ(i, jj)], acc[i][ZZ(i, jj)], 0, 0, 0);
+      MFMA_SNAKE(4, accx, af[i][1], b1);
+      MFMA_SNAKE(4, acc, af[i][0], b1);
     };
     if constexpr (!STAGGER) {
       // (a two-stage ring -- half the LDS, two workgroups per CU hide each other's waits -- has one step in flight)
@@ -748,28 +782,17 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2_kernel(const ConvK 
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = acc[i][j] + accx[i][j] * LIMB2_UNSCALE;
-    if (dp) dp_tile += nblk; else u += k_end - k_begin;
+      for (int j = 0; j < 4; ++j) acc[i][j] = limb_fold(acc[i][j], accx[i][j]);
+    sk.advance(dp_tile, u, it);
     if (SK && (k_begin != 0 || k_end != KT)) {
       // a piece goes to the workspace in the operands' own units (exact: powers of two, one after the other)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (acc[i][j] * unscale_a) * unscale_b;
-      float* slot = a.ws + ((size_t)swz * 2 + (u - (k_end - k_begin) == u_begin ? 0 : 1)) * (BM * BN);
+      acc_unscale(acc, unscale_a, unscale_b);
+      float* slot = StreamK::piece_of<BM * BN>(a.ws, swz, u - (k_end - k_begin), u_begin);
       conv_store_partial<BN, 4, 4, 16>(slot, acc, wm, wn, lane);
       continue;
     }
-    // (the epilogue folds the two exact unscale factors into its per-column constants; if their PRODUCT left the normal
-    //  range -- tensors with max|x| around 2^-50 and less -- apply them here, one after the other, as the pieces do)
     float ua = unscale_a, ub = unscale_b;
-    if (const float u = ua * ub; !(u >= 0x1p-100f && u <= 0x1p100f)) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (acc[i][j] * ua) * ub;
-      ua = ub = 1.f;
-    }
+    acc_unscale_unless_folded(acc, ua, ub);
     __syncthreads();
     if (a.yl != nullptr) l2_epilogue_limbs<WM, WN, false>(a, acc, lds, m0, n0, wm, wn, lane, ua, ub);
     else l2_epilogue<WM, WN>(a, acc, lds, tile_m, m0, n0, wm, wn, lane, ua, ub);
@@ -800,12 +823,8 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2x_kernel(const ConvK
                                                                     unsigned w_bytes, unsigned y_bytes, const float* __restrict__ xamax,
                                                                     const float* __restrict__ wamax) {
   if (a.c.run_if != nullptr && *a.c.run_if == 0) return;  // predicated launch (onda_switch_step decided on the device)
-  constexpr int NW = WM * WN;
-  constexpr int BM = 64 * WM, BN = 64 * WN;
-  constexpr int A_BYTES = BM * 128, STAGE = A_BYTES + BN * 128;  // 128-byte rows: both limbs (see conv_l2_kernel)
-  constexpr int APW = (BM / 8) / NW, BPW = (BN / 8) / NW;        // 8-row pieces per wave and stage
-  static_assert((BM / 8) % NW == 0 && (BN / 8) % NW == 0 && APW % 2 == 0 && BPW % 2 == 0, "whole 16-row blocks per wave");
-  constexpr int DPW = APW + BPW;
+  using T = L2Tile<WM, WN, STAGES>;
+  constexpr int NW = T::NW, BM = T::BM, BN = T::BN, A_BYTES = T::A_BYTES, STAGE = T::STAGE, APW = T::APW, BPW = T::BPW, DPW = T::DPW;
   constexpr int EST = 16;  // buffer stores every wave issues per epilogue (l2_epilogue<.., true>)
   static_assert(STAGES == 3 && DPW + EST <= 63, "ring of three; vmcnt holds 6 bits");
   __shared__ __attribute__((aligned(16))) unsigned char lds[STAGES * STAGE];
@@ -813,13 +832,10 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2x_kernel(const ConvK
   const OndaConv& c = a.c;
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = wave / WN, wn = wave % WN;
-  const int nblk = gridDim.x, bid = blockIdx.x;
-  const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-  const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int nblk = gridDim.x, bid = blockIdx.x, swz = xcd_band(bid, nblk);
   const int KT = a.taps * a.kcper;
-  const int tiles_all = a.tilesM * a.tilesN, tiles_dp = a.tiles_dp;
-  const long long U = (long long)(tiles_all - tiles_dp) * KT;
-  const long long u_begin = swz * U / nblk, u_end = (swz + 1) * U / nblk;
+  const StreamK sk(a.tilesM * a.tilesN, a.tiles_dp, KT, nblk);
+  const long long u_begin = sk.begin(swz), u_end = sk.begin(swz + 1);
   const int wstride = a.taps * c.Cin;
   const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.w, w_bytes);
   __amdgpu_buffer_rsrc_t rx = make_rsrc(a.x, 0);  // (the window of the item being issued: open_issue_item)
@@ -829,13 +845,13 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2x_kernel(const ConvK
   const unsigned cq[2] = {dma_chunk16(lane, 0), dma_chunk16(lane, 1)};
   const int fr0 = frag_ofs(lane, 0), fr1 = frag_ofs(lane, 1);
 
-  // ---- work items: (tile, k_begin, k_end); a cursor is (whole tile index, stream-K unit) ------------------------------
+  // ---- work items: (tile, k_begin, k_end); a cursor is (whole tile index, stream-K unit): StreamK, conv_common.h ---------
   struct Cursor {
     int dp_tile;
     long long u;
   };
-  auto item_valid = [&](const Cursor& cu) { return cu.dp_tile < tiles_dp || cu.u < u_end; };
-  auto item_of = [&](const Cursor& cu, int& tile, int& k_begin, int& k_end) {
+  const int tiles_dp = sk.tiles_dp;
+  auto item_of = [&](const Cursor& cu, int& tile, int& k_begin, int& k_end) {  // (StreamK::item with ONE branch: this kernel's code depends on it)
     if (cu.dp_tile < tiles_dp) {
       tile = cu.dp_tile;
       k_begin = 0;
@@ -846,10 +862,10 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2x_kernel(const ConvK
       k_end = (int)min((long long)KT, k_begin + (u_end - cu.u));
     }
   };
+  auto item_valid = [&](const Cursor& cu) { return sk.valid(cu.dp_tile, cu.u, u_end); };
   auto item_next = [&](Cursor& cu, int k_begin, int k_end) {
-    if (cu.dp_tile < tiles_dp) cu.dp_tile += nblk; else cu.u += k_end - k_begin;
+    sk.advance(cu.dp_tile, cu.u, SkItem{cu.dp_tile < tiles_dp, 0, k_begin, k_end});
   };
-
   // ---- issue side ------------------------------------------------------------------------------------------------------
   Cursor ci{swz, u_begin};
   int i_left = 0;  // K-steps of the issue item still to be issued
@@ -857,11 +873,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2x_kernel(const ConvK
   int tap_i = 0, c0_i = 0;
   unsigned bofs[BPW], aofs[APW];
   int st_issue = 0, st_read = 0, in_flight = 0;  // in_flight: issued steps whose DMAs have not been waited for
-  auto set_tap = [&](int tp) {
-    const int rr = tp / c.kw, ss = tp - rr * c.kw;
-#pragma unroll
-    for (int d = 0; d < APW; ++d) aofs[d] = row_tap_ofs(rp[d], rr, ss, c, cq[d & 1]);
-  };
+  auto set_tap = [&](int tp) { tap_offsets(aofs, rp, tp, c, cq); };
   auto open_issue_item = [&]() {  // row decomposition of the item at `ci` (the VALU work that used to start every tile)
     int tile, k_begin, k_end;
     item_of(ci, tile, k_begin, k_end);
@@ -899,7 +911,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2x_kernel(const ConvK
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)dst, 16, bofs[d], sb, 0, 0);
     }
 #endif
-    st_issue = st_issue + STAGE == STAGES * STAGE ? 0 : st_issue + STAGE;
+    st_issue = ring_next<T>(st_issue);
     ++in_flight;
     --i_left;
     c0_i += BK;
@@ -918,13 +930,10 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2x_kernel(const ConvK
     Ab2 = lds + st_read + wm * 64 * 128 + fr1;
     Bb = lds + st_read + A_BYTES + wn * 64 * 128 + fr0;
     Bb2 = lds + st_read + A_BYTES + wn * 64 * 128 + fr1;
-    st_read = st_read + STAGE == STAGES * STAGE ? 0 : st_read + STAGE;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) af[i][0] = *reinterpret_cast<const f16x8*>(Ab + i * 2048);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) af[i][1] = *reinterpret_cast<const f16x8*>(Ab2 + i * 2048);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const f16x8*>(Bb2 + j * 2048);
+    st_read = ring_next<T>(st_read);
+    FRAG_READ4(af[j][0], Ab);
+    FRAG_READ4(af[j][1], Ab2);
+    FRAG_READ4(bf[j], Bb2);
   };
   int stores_young = 0;  // waits during which an epilogue's stores are still younger than the DMAs waited for
   const bool limb_out = a.yl != nullptr;  // limb-plane output: two 8-byte stores where the fp32 output has one of 16 bytes
@@ -960,12 +969,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2x_kernel(const ConvK
     const bool first_piece = cc.dp_tile >= tiles_dp && cc.u == u_begin;
     item_next(cc, k_begin, k_end);
     f32x4 acc[4][4], accx[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[i][j][e] = accx[i][j][e] = 0.f;
+    acc_clear(acc, accx);
     for (int kt = k_begin; kt < k_end; ++kt) {
       wait_step();
       __builtin_amdgcn_s_barrier();  // everybody's DMAs of this step have landed; the stage read one step ago is free
@@ -976,48 +980,27 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2x_kernel(const ConvK
       // the vmcnt arithmetic of wait_step is unchanged)
       if (!late) issue_step();
       prepare();
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) accx[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][0], bf[ZZ(i, jj)], accx[i][ZZ(i, jj)], 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const f16x8*>(Bb + j * 2048);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) accx[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][1], bf[ZZ(i, jj)], accx[i][ZZ(i, jj)], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) acc[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][0], bf[ZZ(i, jj)], acc[i][ZZ(i, jj)], 0, 0, 0);
+      MFMA_SNAKE(4, accx, af[i][0], bf);
+      FRAG_READ4(bf[j], Bb);
+      MFMA_SNAKE(4, accx, af[i][1], bf);
+      MFMA_SNAKE(4, acc, af[i][0], bf);
       if (late) issue_step();
     }
     stamp();
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = acc[i][j] + accx[i][j] * LIMB2_UNSCALE;
+      for (int j = 0; j < 4; ++j) acc[i][j] = limb_fold(acc[i][j], accx[i][j]);
     if (!whole) {  // stream-K piece: raw accumulators to this workgroup's slot (64 unconditional stores per lane)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (acc[i][j] * unscale_a) * unscale_b;
-      float* slot = a.ws + ((size_t)swz * 2 + (first_piece ? 0 : 1)) * (BM * BN);
+      acc_unscale(acc, unscale_a, unscale_b);
+      float* slot = StreamK::piece_of<BM * BN>(a.ws, swz, first_piece ? 0 : 1, 0);
       conv_store_partial<BN, 4, 4, 16>(slot, acc, wm, wn, lane);
       stores_young = 2;
       stamp();
       continue;
     }
-    // (the epilogue folds the two exact unscale factors into its per-column constants; if their PRODUCT left the normal
-    //  range -- tensors with max|x| around 2^-50 and less -- apply them here, one after the other, as the pieces do)
     float ua = unscale_a, ub = unscale_b;
-    if (const float u = ua * ub; !(u >= 0x1p-100f && u <= 0x1p100f)) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (acc[i][j] * ua) * ub;
-      ua = ub = 1.f;
-    }
+    acc_unscale_unless_folded(acc, ua, ub);
     // every wave has its fragments of the last step (they fed its MFMAs): that stage is scratch now.  A bare barrier:
     // the DMAs of the next two steps stay in flight (see l2_epilogue)
     __builtin_amdgcn_s_barrier();
@@ -1107,9 +1090,7 @@ __global__ __launch_bounds__(512, 2) void conv_l2a_kernel(const ConvK a, unsigne
 #define ONDA_L2A_STAGGER 0
 #endif
   const bool late = ONDA_L2A_STAGGER && wave >= NW / 2;  // the second wave of its SIMD takes its epilogue slice first (measurement switch)
-  const int nblk = gridDim.x, bid = blockIdx.x;
-  const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7;
-  const int swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int nblk = gridDim.x, bid = blockIdx.x, swz = xcd_band(bid, nblk);
   const long long items = (long long)a.tilesM * a.tilesN;
   const int it_begin = (int)(swz * items / nblk), it_end = (int)((swz + 1) * items / nblk);
   if (it_begin >= it_end) return;
@@ -1119,7 +1100,7 @@ __global__ __launch_bounds__(512, 2) void conv_l2a_kernel(const ConvK a, unsigne
   const Scale2 sx = scale_of(xamax), sw = scale_of(wamax);
   // the two exact unscale factors are folded into the epilogue's per-column constants -- unless their PRODUCT leaves the normal
   // range (tensors with max|x| around 2^-50): then they are applied to the sums, one after the other (pre_a, pre_b)
-  const bool unscale_first = !(sx.inv * sw.inv >= 0x1p-100f && sx.inv * sw.inv <= 0x1p100f);
+  const bool unscale_first = !(sx.inv * sw.inv >= 0x1p-100f && sx.inv * sw.inv <= 0x1p100f);  // (unscale_folds, written out: experiments.md)
   const float ua = unscale_first ? 1.f : sx.inv, ub = unscale_first ? 1.f : sw.inv;
   const float pre_a = unscale_first ? sx.inv : 1.f, pre_b = unscale_first ? sw.inv : 1.f;
   const int lrow = lane >> 3;
@@ -1351,12 +1332,7 @@ __global__ __launch_bounds__(512, 2) void conv_l2a_kernel(const ConvK a, unsigne
     }
     stamp();
     f32x4 acc[MI][4], accx[MI][4];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[i][j][e] = accx[i][j][e] = 0.f;
+    acc_clear(acc, accx);
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
       asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NWAIT) : "memory");  // this wave's DMAs of this step have landed (and its LDS writes)
@@ -1366,8 +1342,7 @@ __global__ __launch_bounds__(512, 2) void conv_l2a_kernel(const ConvK a, unsigne
       const unsigned char* Bb2 = lds + st_read + wn * 64 * 128 + fr1;
       st_read = st_read + STAGE == NST * STAGE ? 0 : st_read + STAGE;
       f16x8 bf[4], a2[MI];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const f16x8*>(Bb2 + j * 2048);
+      FRAG_READ4(bf[j], Bb2);
       if constexpr (A2L) {
 #pragma unroll
         for (int i = 0; i < MI; ++i) a2[i] = *reinterpret_cast<const f16x8*>(a2lds + ((kb * (BM / 16) + wm * MI + i) << 10) + fa2o);
@@ -1380,20 +1355,10 @@ __global__ __launch_bounds__(512, 2) void conv_l2a_kernel(const ConvK a, unsigne
       // instructions beside the other's MFMAs, in every K-step (the slot stagger of conv_l2_kernel, with the epilogue as the
       // "prepare" slot).  Same instructions per wave either way: the counted wait above does not notice.
       if (late) ep_step(kb);
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) accx[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[kb][i][0], bf[ZZ(i, jj)], accx[i][ZZ(i, jj)], 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const f16x8*>(Bb + j * 2048);
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) accx[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[i], bf[ZZ(i, jj)], accx[i][ZZ(i, jj)], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) acc[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[kb][i][0], bf[ZZ(i, jj)], acc[i][ZZ(i, jj)], 0, 0, 0);
+      MFMA_SNAKE(MI, accx, af[kb][i][0], bf);
+      FRAG_READ4(bf[j], Bb);
+      MFMA_SNAKE(MI, accx, a2[i], bf);
+      MFMA_SNAKE(MI, acc, af[kb][i][0], bf);
 #ifdef ONDA_L2A_STEP_STAMPS  // (measurement builds: a branch per K-step, which keeps the compiler from interleaving the slice with the MFMAs)
       if (a.stamps != nullptr && t == 0 && item == it_begin + 2) a.stamps[(size_t)bid * 32 + 16 + kb] = __builtin_amdgcn_s_memtime();
 #endif
@@ -1404,7 +1369,7 @@ __global__ __launch_bounds__(512, 2) void conv_l2a_kernel(const ConvK a, unsigne
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) old[i][j] = ((acc[i][j] + accx[i][j] * LIMB2_UNSCALE) * pre_a) * pre_b;
+      for (int j = 0; j < 4; ++j) old[i][j] = unscale2(limb_fold(acc[i][j], accx[i][j]), pre_a, pre_b);
     o_valid = true;
     o_p = p;
     o_m0 = m0;
@@ -1445,15 +1410,15 @@ __global__ __launch_bounds__(256) void conv_l2_fixup_kernel(const ConvK a, int G
   __shared__ int wave_count[4];
   const OndaConv& c = a.c;
   const int KT = a.taps * a.kcper;
-  const long long U = (long long)(a.tilesM * a.tilesN - a.tiles_dp) * KT;
+  const StreamK sk(a.tilesM * a.tilesN, a.tiles_dp, KT, G);
   // grid.x walks every tile of the tile ROWS that hold remainder tiles (a statistic row spans all channel tiles of a tile
   // row, so the extra rows must be complete): tiles of the first such row that ran one-per-workgroup only fill identities
   const int sub = blockIdx.y;
   const int first_m = a.tiles_dp / a.tilesN;
   const int tile = first_m * a.tilesN + blockIdx.x;
   const int lt = tile - a.tiles_dp;  // remainder-local tile (negative: not a remainder tile)
-  const long long t0 = (long long)lt * KT, t1 = t0 + KT;
-  const int vs = lt < 0 ? 0 : (int)(((t0 + 1) * G + U - 1) / U - 1), ve = lt < 0 ? 0 : (int)((t1 * G + U - 1) / U - 1);
+  const SkTile tu = sk.tile_units(lt);
+  const int vs = lt < 0 ? 0 : sk.first_wg(tu), ve = lt < 0 ? 0 : sk.last_wg(tu);
   const int tile_n = tile % a.tilesN, tile_m = tile / a.tilesN;
   const int t = threadIdx.x, col = (t % C4) * 4, rg = t / C4;
   const int n = tile_n * BN + col;
@@ -1473,18 +1438,13 @@ __global__ __launch_bounds__(256) void conv_l2_fixup_kernel(const ConvK a, int G
     return;
   }
   // the workgroups whose K range meets this tile, compacted in ascending order (with fewer remainder K-steps than
-  // workgroups some ranges are empty); entry = workgroup * 2 + (0: its first piece, 1: its second)
+  // workgroups some ranges are empty); entry = the piece's workspace slot
   const int npieces = ve - vs + 1;
   int nvalid = 0;
   for (int p0 = 0; p0 < npieces; p0 += 256) {
     const int p = p0 + t;
     int val = -1;
-    if (p < npieces) {
-      const int vb = vs + p;
-      const long long b0 = (long long)vb * U / G, b1 = (long long)(vb + 1) * U / G;
-      const long long g0 = max(b0, t0), g1 = min(b1, t1);
-      if (g1 > g0) val = vb * 2 + (g0 == b0 ? 0 : 1);
-    }
+    if (p < npieces) val = sk.piece(vs + p, tu);
     const unsigned long long mask = __ballot(val >= 0);
     if ((t & 63) == 0) wave_count[t >> 6] = __popcll(mask);
     __syncthreads();
@@ -1646,11 +1606,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_wgrad_l2_kernel(const 
   // workgroups are dealt round-robin over the 8 XCDs: hand each XCD a contiguous band of the (pixel range, tap,
   // channel tile) order, so that the workgroups that stream the same dy rows (all input-channel tiles of one tap and
   // pixel range) and the same x rows (the taps of one pixel range) find them in one L2
-  int bid;
-  {
-    const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = blockIdx.x & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-  }
+  int bid = xcd_band(blockIdx.x, gridDim.x);
   const int tile_c = bid % a.tilesC;
   bid /= a.tilesC;
   const int tap = bid % a.taps;
@@ -1836,12 +1792,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_wgrad_l2_kernel(const 
   }
 
   f32x4 acc[4][4], accx[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[i][j][e] = accx[i][j][e] = 0.f;
+  acc_clear(acc, accx);
 
   if (stp) {
     stp[1] = __builtin_amdgcn_s_memtime();
@@ -1920,21 +1871,12 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_wgrad_l2_kernel(const 
 #pragma unroll
       for (int j = 0; j < 4; ++j) b1[j] = tr_read8(base + fb[j][0], base + fb[j][1]);
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) accx[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][0], bf[ZZ(i, jj)], accx[i][ZZ(i, jj)], 0, 0, 0);
+    MFMA_SNAKE(4, accx, af[i][0], bf);
     if constexpr (!STAGGER) lds_wait(b1[0], b1[1], b1[2], b1[3]);
     if constexpr (STAGGER) issue_second_part();
     __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) accx[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][1], b1[ZZ(i, jj)], accx[i][ZZ(i, jj)], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) acc[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][0], b1[ZZ(i, jj)], acc[i][ZZ(i, jj)], 0, 0, 0);
+    MFMA_SNAKE(4, accx, af[i][1], b1);
+    MFMA_SNAKE(4, acc, af[i][0], b1);
   };
   if constexpr (MODE >= 1) {
     // MODE 1 / 2 (round 5; MODE 0 above is the loop of rounds 2-4, kept for the four-wave tile and as the fallback).  The stamps
@@ -2038,19 +1980,10 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_wgrad_l2_kernel(const 
         if (late) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DPW) : "memory");
         __builtin_amdgcn_s_barrier();
         offsets(kt_next, t_next, i_iss < nlive ? 0u : PAST);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) accx[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][0], bf[ZZ(i, jj)], accx[i][ZZ(i, jj)], 0, 0, 0);
+        MFMA_SNAKE(4, accx, af[i][0], bf);
         issue_first();
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) accx[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][1], b1[ZZ(i, jj)], accx[i][ZZ(i, jj)], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) acc[i][ZZ(i, jj)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][0], b1[ZZ(i, jj)], acc[i][ZZ(i, jj)], 0, 0, 0);
+        MFMA_SNAKE(4, accx, af[i][1], b1);
+        MFMA_SNAKE(4, acc, af[i][0], b1);
         // the order the scheduler is asked for: the offsets' VALU two per MFMA under the first 16, then one DMA (its m0, its
         // address add) per two MFMAs, then the rest of the MFMAs
         constexpr int NI = DPW / 2;
@@ -2115,7 +2048,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_wgrad_l2_kernel(const 
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = ((acc[i][j] + accx[i][j] * LIMB2_UNSCALE) * unscale_a) * unscale_b;
+    for (int j = 0; j < 4; ++j) acc[i][j] = unscale2(limb_fold(acc[i][j], accx[i][j]), unscale_a, unscale_b);
   if (stp) stp[2] = __builtin_amdgcn_s_memtime();
   __syncthreads();
   // slab store through the wave's own 4 KiB of LDS: 16 rows (output channels) x 64 input channels at a time, 16-byte stores
@@ -2248,7 +2181,7 @@ L2Plan l2_plan(long long M, int Cout, int taps, int Cin, bool have_ws, long long
   const double t_tile_us = 2.0 * q.BM * q.BN * taps * Cin / 1.4e6;  // one tile on one CU at ~360 TF/s chip-wide
   const double fix_us = 6.0 + (q.G + 2.0 * q.rem) * (q.BM * q.BN / 16384.0) * 0.02;  // partial tiles written + read
   q.balanced = have_ws && q.rem != 0 && KT >= 4 && t_tile_us * (1.0 - (double)q.rem / q.G) > fix_us &&
-               (size_t)q.G * 2 * q.BM * q.BN <= (size_t)onda_conv_ws_floats() && q.G <= 1024;
+               StreamK::ws_floats(q.G, q.BM * q.BN) <= (size_t)onda_conv_ws_floats() && q.G <= 1024;
   if (plain_schedule) q.balanced = false;  // OndaConv.plain_schedule
   // 1 x 1 convolutions with 64 / 128 / 256 input channels and at least two column tiles (with one, nothing amortises a
   // panel's rows) run ACTIVATION-STATIONARY where the 128 x 128 tiles would (conv_l2a_kernel: a workgroup's 128 rows in
