@@ -317,6 +317,28 @@ int onda_gn_bwd(const float* dout, int lddo, const float* out, int ldo, const fl
                 const float* chmul, const float* mean, const float* rstd, float* dx, float* dgamma, float* dbeta,
                 float* ws, int B, int64_t HW, int C, int groups, int relu, onda_stream_t s);
 
+/* GroupNorm on a backbone convolution (the stem and the four shortcut norms of DeepLabv2-Resnet50-GN; affine usually frozen):
+ * out = [relu]((x - mean[b,g]) * rstd[b,g] * gamma + beta) on dense rows x[B][HW][C].  C / groups is 2 (one 16-byte access
+ * spans two groups) or a multiple of 4, C % 4 == 0; anything else is ONDA_EINVAL.  Statistics per (image, group), biased
+ * variance, combined in double:
+ *   stats == NULL: one reduction pass over x (ws: onda_gn_site_ws floats);
+ *   stats != NULL: the partials [tiles][stat_rows][C] the convolution that produced x left behind (stat_rows 2 or 4: sum, sum of
+ *     squares first; tile_rows GEMM rows per partial row, onda_conv_l2_tiles_m_split) -- no pass over x.  Legal when no tile
+ *     lies across two images and the table has one row per tile row: HW % tile_rows == 0 and tiles == B * HW / tile_rows
+ *     (a stream-K remainder appends rows); ONDA_EINVAL otherwise, and the caller takes the reduction pass.
+ * mean / rstd [B * groups] are written for the backward pass; amax: NULL or the running max|out| (f16x2 section);
+ * run_if: NULL or a device int32 -- when it reads 0 every launch of the call returns at once (OndaConv.run_if). */
+int64_t onda_gn_site_ws(int B, int64_t HW, int C);
+int onda_gn_site_fwd(const float* x, const float* stats, int tiles, int stat_rows, int tile_rows, const float* gamma,
+                     const float* beta, float* out, float* mean, float* rstd, float* ws, int B, int64_t HW, int C, int groups,
+                     float eps, int relu, float* amax, const int32_t* run_if, onda_stream_t s);
+/* backward: g = dout * (out > 0 if relu); dx = rstd * (gamma * g - (ds + xhat * dq) / n), max|dx| into amax (NULL or the running
+ * maximum: dx is the dy of the convolution below); dgamma / dbeta optional (NULL: frozen affine, not computed).  Fixed
+ * reduction order, no float atomics on the sums.  ws: onda_gn_site_ws floats. */
+int onda_gn_site_bwd(const float* dout, const float* out, const float* x, const float* gamma, const float* mean,
+                     const float* rstd, float* dx, float* dgamma, float* dbeta, float* ws, int B, int64_t HW, int C,
+                     int groups, int relu, float* amax, onda_stream_t s);
+
 /* ---- MaxPool 3x3 s2 p1 ceil_mode (deeplabv2.py:289-291), NHWC; idx = winning window slot -- */
 int onda_maxpool_fwd(const float* x, float* y, uint8_t* idx, int B, int Hi, int Wi, int C, int Ho, int Wo,
                      onda_stream_t s);

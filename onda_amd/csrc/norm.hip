@@ -32,7 +32,8 @@ static inline ColPlan col_plan(int B, int64_t HW, int C) {
 
 template <class F>
 __global__ __launch_bounds__(256) void colreduce_kernel(F f, int64_t HW, int C, int cx, int64_t rows_per_chunk,
-                                                        float* __restrict__ partials) {
+                                                        float* __restrict__ partials, const int32_t* run_if) {
+  if (run_if != nullptr && *run_if == 0) return;  // predicated launch (onda_gn_site_fwd)
   __shared__ f32x4 red[2][256];
   const int t = threadIdx.x;
   const int ry_n = 256 / cx;
@@ -65,9 +66,10 @@ __global__ __launch_bounds__(256) void colreduce_kernel(F f, int64_t HW, int C, 
 }
 
 template <class F>
-static int launch_colreduce(const F& f, int B, int64_t HW, int C, float* partials, const ColPlan& p, hipStream_t s) {
+static int launch_colreduce(const F& f, int B, int64_t HW, int C, float* partials, const ColPlan& p, hipStream_t s,
+                            const int32_t* run_if = nullptr) {
   dim3 grid(p.gridx, p.chunks, B);
-  hipLaunchKernelGGL((colreduce_kernel<F>), grid, dim3(256), 0, s, f, HW, C, p.cx, p.rows_per_chunk, partials);
+  hipLaunchKernelGGL((colreduce_kernel<F>), grid, dim3(256), 0, s, f, HW, C, p.cx, p.rows_per_chunk, partials, run_if);
   return ONDA_LAUNCH_RESULT();
 }
 
@@ -336,7 +338,7 @@ __global__ __launch_bounds__(256) void pair_finalize_kernel(const float* __restr
 __global__ void gn_bwd_group_kernel(const float* __restrict__ AB, int B, int C, int groups,
                                     const float* __restrict__ gamma, float* __restrict__ dgamma,
                                     float* __restrict__ dbeta, float* __restrict__ gsum /*[B][groups][2]*/) {
-  for (int ch = threadIdx.x; ch < C; ch += blockDim.x) {
+  for (int ch = threadIdx.x; ch < C && (dgamma || dbeta); ch += blockDim.x) {  // (frozen affine: neither is asked for)
     float da = 0.f, db = 0.f;
     for (int b = 0; b < B; ++b) {
       db += AB[((size_t)b * 2 + 0) * C + ch];
@@ -387,6 +389,139 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
     const f32x4 v = rs * (LD4(gamma + col) * g - (gsum[gi * 2] + xh * gsum[gi * 2 + 1]) * inv_n);
     *reinterpret_cast<f32x4*>(dx + row * C + col) = v;
   }
+}
+
+// ---- GroupNorm on a backbone convolution ------------------------------------------------------
+// The stem and the four shortcuts of DeepLabv2-Resnet50-GN: dense [B][HW][C] rows, 2 channels per group (the stem: one f32x4
+// spans two groups) or a multiple of 4.  Statistics from the reduction pass or from the conv epilogue's tile partials; a
+// device predicate on every forward launch; max|out| / max|dx| left behind for the convolutions on either side.
+__device__ __forceinline__ void gn_site_stats(const float* __restrict__ mean, const float* __restrict__ rstd, int b,
+                                              int groups, int cpg, int col, f32x4& mu, f32x4& rs) {
+  const int g0 = b * groups + col / cpg;
+  const int g1 = cpg == 2 ? g0 + 1 : g0;  // columns col + 2, col + 3
+  const float m0 = mean[g0], m1 = mean[g1], r0 = rstd[g0], r1 = rstd[g1];
+  mu = f32x4{m0, m0, m1, m1};
+  rs = f32x4{r0, r0, r1, r1};
+}
+
+// gn_finalize_kernel over either table: image b owns rows [b * rows, (b + 1) * rows) of `row_stride` floats each, the sums in
+// the first C of them and the sums of squares in the next C ([b][chunk][2][C] of colreduce_kernel, [tile][stat_rows][C] of a
+// conv epilogue whose tiles do not straddle two images).
+__global__ __launch_bounds__(256) void gn_site_finalize_kernel(const float* __restrict__ partials, int rows,
+                                                               int64_t row_stride, int C, int groups, double count,
+                                                               float eps, float* mean, float* rstd,
+                                                               const int32_t* run_if) {
+  if (run_if != nullptr && *run_if == 0) return;
+  __shared__ double red[2][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int idx = blockIdx.x;
+  const int b = idx / groups, g = idx % groups, cpg = C / groups;
+  double s1 = 0.0, s2 = 0.0;
+  for (int i = threadIdx.x; i < rows * cpg; i += 256) {
+    const int k = i / cpg, j = i - k * cpg;
+    const size_t base = ((size_t)b * rows + k) * row_stride + g * cpg + j;
+    s1 += (double)partials[base];
+    s2 += (double)partials[base + C];
+  }
+  s1 = wave_sum_d(s1);
+  s2 = wave_sum_d(s2);
+  if (lane == 0) {
+    red[0][wave] = s1;
+    red[1][wave] = s2;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  s1 = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+  s2 = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+  const double mu = s1 / count;
+  double var = s2 / count - mu * mu;
+  if (var < 0.0) var = 0.0;
+  mean[idx] = (float)mu;
+  rstd[idx] = (float)(1.0 / sqrt(var + (double)eps));
+}
+
+__global__ __launch_bounds__(256) void gn_site_apply_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, float* __restrict__ out,
+                                                            const float* __restrict__ mean,
+                                                            const float* __restrict__ rstd, int64_t HW, int C, int groups,
+                                                            size_t total4, int relu, float* __restrict__ amax,
+                                                            const int32_t* run_if) {
+  if (run_if != nullptr && *run_if == 0) return;
+  const int c4 = C / 4, cpg = C / groups;
+  float mx = 0.f;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total4; e += (size_t)gridDim.x * blockDim.x) {
+    const int col = (int)(e % c4) * 4;
+    const int b = (int)(e / c4 / HW);
+    f32x4 mu, rs;
+    gn_site_stats(mean, rstd, b, groups, cpg, col, mu, rs);
+    f32x4 v = (LD4(x + e * 4) - mu) * rs * LD4(gamma + col) + LD4(beta + col);
+    if (relu) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
+    }
+    *reinterpret_cast<f32x4*>(out + e * 4) = v;
+    mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+  }
+  __shared__ float amax_red[4];
+  if (amax != nullptr) amax_update_block(amax, mx, amax_red);
+}
+
+struct GnSiteBwdRed {  // g = dout*(out>0); a = g, b = g*xhat
+  const float* dout;
+  const float* out;
+  const float* x;
+  const float* mean;
+  const float* rstd;
+  int64_t HW;
+  int C, groups, relu;
+  __device__ void operator()(int b, int64_t r, int col, f32x4& a, f32x4& bb) const {
+    const size_t o = ((size_t)b * HW + r) * C + col;
+    f32x4 g = LD4(dout + o);
+    if (relu) {
+      const f32x4 ov = LD4(out + o);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) g[j] = ov[j] > 0.f ? g[j] : 0.f;
+    }
+    f32x4 mu, rs;
+    gn_site_stats(mean, rstd, b, groups, C / groups, col, mu, rs);
+    a = g;
+    bb = g * ((LD4(x + o) - mu) * rs);
+  }
+};
+
+__global__ __launch_bounds__(256) void gn_site_bwd_apply_kernel(const float* __restrict__ dout,
+                                                                const float* __restrict__ out,
+                                                                const float* __restrict__ x,
+                                                                const float* __restrict__ gamma,
+                                                                const float* __restrict__ mean,
+                                                                const float* __restrict__ rstd,
+                                                                const float* __restrict__ gsum, float* __restrict__ dx,
+                                                                int64_t HW, int C, int groups, size_t total4, float inv_n,
+                                                                int relu, float* __restrict__ amax) {
+  const int c4 = C / 4, cpg = C / groups;
+  float mx = 0.f;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total4; e += (size_t)gridDim.x * blockDim.x) {
+    const int col = (int)(e % c4) * 4;
+    const int b = (int)(e / c4 / HW);
+    f32x4 g = LD4(dout + e * 4);
+    if (relu) {
+      const f32x4 ov = LD4(out + e * 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) g[j] = ov[j] > 0.f ? g[j] : 0.f;
+    }
+    f32x4 mu, rs;
+    gn_site_stats(mean, rstd, b, groups, cpg, col, mu, rs);
+    const int g0 = b * groups + col / cpg;
+    const int g1 = cpg == 2 ? g0 + 1 : g0;
+    const f32x4 ds = {gsum[g0 * 2], gsum[g0 * 2], gsum[g1 * 2], gsum[g1 * 2]};
+    const f32x4 dq = {gsum[g0 * 2 + 1], gsum[g0 * 2 + 1], gsum[g1 * 2 + 1], gsum[g1 * 2 + 1]};
+    const f32x4 xh = (LD4(x + e * 4) - mu) * rs;
+    const f32x4 v = rs * (LD4(gamma + col) * g - (ds + xh * dq) * inv_n);
+    *reinterpret_cast<f32x4*>(dx + e * 4) = v;
+    mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+  }
+  __shared__ float amax_red[4];
+  if (amax != nullptr) amax_update_block(amax, mx, amax_red);
 }
 
 __global__ __launch_bounds__(256) void colsum_finalize_kernel(const float* __restrict__ partials, int chunks, int B,
@@ -506,6 +641,66 @@ int onda_gn_bwd(const float* dout, int lddo, const float* out, int ldo, const fl
   hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, ONDA_STREAM(s), dout, lddo, out, ldo, x,
                      ldx, gamma, chmul, mean, rstd, gsum, dx, HW, C, groups, total4,
                      (float)(1.0 / ((double)HW * (C / groups))), relu);
+  return ONDA_LAUNCH_RESULT();
+}
+
+static inline bool gn_site_shape_ok(int B, int64_t HW, int C, int groups) {
+  if (B < 1 || HW < 1 || C < 4 || groups < 1 || C % 4 != 0 || C % groups != 0) return false;
+  const int cpg = C / groups;
+  return cpg == 2 || cpg % 4 == 0;
+}
+
+int64_t onda_gn_site_ws(int B, int64_t HW, int C) {
+  const ColPlan p = col_plan(B, HW, C);
+  return (int64_t)B * p.chunks * 2 * C + (int64_t)B * 2 * C + (int64_t)B * C;
+}
+
+int onda_gn_site_fwd(const float* x, const float* stats, int tiles, int stat_rows, int tile_rows, const float* gamma,
+                     const float* beta, float* out, float* mean, float* rstd, float* ws, int B, int64_t HW, int C, int groups,
+                     float eps, int relu, float* amax, const int32_t* run_if, onda_stream_t s) {
+  ONDA_REQUIRE(x && gamma && beta && out && mean && rstd && gn_site_shape_ok(B, HW, C, groups));
+  if (!ONDA_ALIGNED16(x) || !ONDA_ALIGNED16(out) || !ONDA_ALIGNED16(gamma) || !ONDA_ALIGNED16(beta)) return ONDA_EALIGN;
+  const double count = (double)HW * (C / groups);
+  if (stats != nullptr) {
+    // one partial row per tile row and no tile across two images (a stream-K remainder appends rows: not taken)
+    ONDA_REQUIRE((stat_rows == 2 || stat_rows == 4) && tile_rows > 0 && HW % tile_rows == 0 &&
+                 (int64_t)tiles == (int64_t)B * (HW / tile_rows));
+    hipLaunchKernelGGL(gn_site_finalize_kernel, dim3(B * groups), dim3(256), 0, ONDA_STREAM(s), stats,
+                       (int)(HW / tile_rows), (int64_t)stat_rows * C, C, groups, count, eps, mean, rstd, run_if);
+  } else {
+    ONDA_REQUIRE(ws != nullptr);
+    const ColPlan p = col_plan(B, HW, C);
+    SqStats f{x, HW, C};
+    int rc = launch_colreduce(f, B, HW, C, ws, p, ONDA_STREAM(s), run_if);
+    if (rc) return rc;
+    hipLaunchKernelGGL(gn_site_finalize_kernel, dim3(B * groups), dim3(256), 0, ONDA_STREAM(s), ws, p.chunks,
+                       (int64_t)2 * C, C, groups, count, eps, mean, rstd, run_if);
+  }
+  const size_t total4 = (size_t)B * HW * C / 4;
+  hipLaunchKernelGGL(gn_site_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, ONDA_STREAM(s), x, gamma, beta, out, mean,
+                     rstd, HW, C, groups, total4, relu, amax, run_if);
+  return ONDA_LAUNCH_RESULT();
+}
+
+int onda_gn_site_bwd(const float* dout, const float* out, const float* x, const float* gamma, const float* mean,
+                     const float* rstd, float* dx, float* dgamma, float* dbeta, float* ws, int B, int64_t HW, int C,
+                     int groups, int relu, float* amax, onda_stream_t s) {
+  ONDA_REQUIRE(dout && x && gamma && mean && rstd && dx && ws && (!relu || out) && gn_site_shape_ok(B, HW, C, groups));
+  if (!ONDA_ALIGNED16(dout) || !ONDA_ALIGNED16(x) || !ONDA_ALIGNED16(dx) || !ONDA_ALIGNED16(gamma) ||
+      (relu && !ONDA_ALIGNED16(out)))
+    return ONDA_EALIGN;
+  const ColPlan p = col_plan(B, HW, C);
+  float* AB = ws + (size_t)B * p.chunks * 2 * C;
+  float* gsum = AB + (size_t)B * 2 * C;
+  GnSiteBwdRed f{dout, out, x, mean, rstd, HW, C, groups, relu};
+  int rc = launch_colreduce(f, B, HW, C, ws, p, ONDA_STREAM(s));
+  if (rc) return rc;
+  hipLaunchKernelGGL(pair_finalize_kernel, dim3((B * C + 3) / 4), dim3(256), 0, ONDA_STREAM(s), ws, p.chunks, B, C, AB);
+  hipLaunchKernelGGL(gn_bwd_group_kernel, dim3(1), dim3(256), 0, ONDA_STREAM(s), AB, B, C, groups, gamma, dgamma, dbeta,
+                     gsum);
+  const size_t total4 = (size_t)B * HW * C / 4;
+  hipLaunchKernelGGL(gn_site_bwd_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, ONDA_STREAM(s), dout, out, x, gamma,
+                     mean, rstd, gsum, dx, HW, C, groups, total4, (float)(1.0 / ((double)HW * (C / groups))), relu, amax);
   return ONDA_LAUNCH_RESULT();
 }
 

@@ -5,15 +5,20 @@ import torch
 
 from onda_amd.framework.model.deeplabv2 import get_deeplab_v2
 
-MODEL_NAMES = ["DeepLabv2-Resnet50", "DeepLabv2-Resnet101"]
-_LAYERS = {"DeepLabv2-Resnet50": [3, 4, 6, 3], "DeepLabv2-Resnet101": [3, 4, 23, 3]}
+MODEL_NAMES = ["DeepLabv2-Resnet50", "DeepLabv2-Resnet101", "DeepLabv2-Resnet50-GN"]
+_LAYERS = {"DeepLabv2-Resnet50": [3, 4, 6, 3], "DeepLabv2-Resnet101": [3, 4, 23, 3], "DeepLabv2-Resnet50-GN": [3, 4, 6, 3]}
 
 
 def get_model(cfg, n_classes):
     assert cfg.MODEL.NAME in MODEL_NAMES, f"cfg.MODEL.NAME should be in {MODEL_NAMES} (the HIP path covers the DeepLabV2 ResNets)"
+    kw = {}
+    if cfg.MODEL.NAME == "DeepLabv2-Resnet50-GN":
+        # the reference's lambda (:33); its _make_layer never hands it to the blocks, so it reaches the stem's bn1 and the
+        # four layerN.0.downsample.1 only -- the blocks keep their BatchNorms
+        kw["norm_module"] = lambda *k, **x: torch.nn.GroupNorm(32, *k, **x)
     # built multi_level=True like the reference, so the (never executed) layer5 head is part of the state_dict
     model = get_deeplab_v2(num_classes=n_classes, layers=_LAYERS[cfg.MODEL.NAME], multi_level=True,
-                           classifier=cfg.MODEL.CLASSIFIER)
+                           classifier=cfg.MODEL.CLASSIFIER, **kw)
     load = cfg.MODEL.LOAD
     if load is not None and load != "None" and not (isinstance(load, dict) and not load):
         state = torch.load(load, map_location="cpu")

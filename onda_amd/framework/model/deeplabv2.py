@@ -8,7 +8,9 @@ What is kept from the reference: ``get_deeplab_v2(...)`` and its arg
 ``nn.BatchNorm2d`` instances whose ``momentum`` / ``track_running_stats`` are read at forward
 time, ``deepcopy`` works, and ``optim_parameters(lr)`` walks the tree exactly as :397-439 do
 (duplicate entries included); the construction order and init recipe (:210-241, :326-331),
-so a given torch seed produces the same initial weights.
+so a given torch seed produces the same initial weights.  ``norm_module`` may be the handler's GroupNorm lambda
+(``DeepLabv2-Resnet50-GN``): as in the reference it reaches the stem's ``bn1`` and the four ``layerN.0.downsample.1`` only
+(361 keys), which then run on ``ops.GNSiteFn``.
 
 What is different: inside ``forward`` activations are NHWC and every op is a HIP kernel;
 `feat` / `out` come back as NCHW-shaped views of pixel-major buffers (no copy), which is
@@ -72,6 +74,13 @@ def conv_bn(conv, bn, x, relu, residual=None):
     statistics move only while ``track_running_stats`` (adaptation_model.py:29-36).
     eval mode (static / dynamic models, evaluation): BN folded into the conv epilogue."""
     k, stride, dil, pad = conv.geom()
+    if isinstance(bn, nn.GroupNorm):
+        # a shortcut of DeepLabv2-Resnet50-GN (the only conv_bn site the reference hands its norm_module to): per-image
+        # statistics, nothing to fold -- the same plain conv + GroupNorm kernels in train and eval mode
+        if residual is not None:
+            raise NotImplementedError("onda_amd: GroupNorm with a residual add is not a site of the reference's models")
+        y, stats = conv(x, want_stats=True)
+        return ops.GNSiteFn.apply(y, stats, bn.weight, bn.bias, relu, bn.num_groups, bn.eps)
     if bn.training:
         # "f16x2" with pre-split operands: the BatchNorm output is written as limb planes only (what the next conv, the
         # residual add and the backward mask read); the conv epilogue then also leaves per-channel extrema (4 stat rows)
@@ -315,6 +324,9 @@ class ResNetMulti(nn.Module):
 
     def _stem(self, x):
         bn = self.bn1
+        if isinstance(bn, nn.GroupNorm):  # DeepLabv2-Resnet50-GN: 2 channels per group, the same in train and eval mode
+            y, stats = ops.StemConvFn.apply(x, self.conv1.weight, self.conv1._pack, True)
+            return ops.MaxPoolFn.apply(ops.GNSiteFn.apply(y, stats, bn.weight, bn.bias, True, bn.num_groups, bn.eps), True)
         if bn.training:
             return self._stem_train(x, self._running(bn))
         return ops.MaxPoolFn.apply(ops.stem_eval(x, self.conv1.weight, self.conv1._pack, *bn.folded()), True)

@@ -60,3 +60,7 @@ SHARE_GRADS = True  # tests turn this off to compare with autograd's own accumul
 # launch it removes).  Built, correct (the whole GPU suite passes with it on), OFF by default; ONDA_FUSE_BN=1 /
 # tools/ab_flag.py onda_amd.ops FUSE_BN_FINALIZE True -- ... to measure it again.
 FUSE_BN_FINALIZE = os.environ.get("ONDA_FUSE_BN", "0") == "1"
+
+# GroupNorm on a backbone convolution (ops.GNSiteFn): statistics from the conv epilogue's tile partials where no tile lies
+# across two images, instead of a reduction pass over the conv output.  tools/gn_timing.py measures both routes.
+GN_FUSED_STATS = os.environ.get("ONDA_GN_FUSED_STATS", "1") == "1"

@@ -291,6 +291,60 @@ class GNConcatFn(torch.autograd.Function):
         return (None, None, *dys, *dgs, *dbs)
 
 
+def gn_site_stats(stats, B, HW):
+    """The conv epilogue's partials when `onda_gn_site_fwd` may take its statistics from them (no tile across two images, one
+    partial row per tile row), else None: the reduction pass."""
+    rows = getattr(stats, "_onda_tile_rows", 0) if stats is not None else 0
+    if _state.GN_FUSED_STATS and rows and HW % rows == 0 and stats.shape[0] == B * (HW // rows):
+        return stats
+    return None
+
+
+class GNSiteFn(torch.autograd.Function):
+    """GroupNorm (+ReLU) on the output of a backbone convolution: the stem and the four shortcuts of DeepLabv2-Resnet50-GN.
+    `stats`: the conv epilogue's sum / sum-of-squares partials or None; they replace the statistics pass over `y` where no
+    tile lies across two images (gn_site_stats).  Per-image statistics: row groups and train / eval mode make no difference.
+    Inside ``ops.predicated`` every launch carries the flag.  dgamma / dbeta only where autograd asks (the sites are frozen)."""
+
+    @staticmethod
+    def forward(ctx, y, stats, gamma, beta, relu, groups=GN_GROUPS, eps=GN_EPS):
+        B, H, W, C = y.shape
+        HW = H * W
+        y = y.contiguous()
+        dev = y.device
+        out = torch.empty_like(y)
+        mean = torch.empty(B * groups, device=dev, dtype=torch.float32)
+        rstd = torch.empty_like(mean)
+        amax = amax_slot(dev) if _state.CONV_MODE == "f16x2" else None  # the output feeds a conv: leave max|out| behind
+        part = gn_site_stats(stats, B, HW)
+        ws = torch.empty(query("onda_gn_site_ws", B, HW, C), device=dev, dtype=torch.float32) if part is None else None
+        call("onda_gn_site_fwd", _p(y), _p(part), part.shape[0] if part is not None else 0,
+             part.shape[1] if part is not None else 0, part._onda_tile_rows if part is not None else 0, _p(gamma), _p(beta),
+             _p(out), _p(mean), _p(rstd), _p(ws), B, HW, C, groups, eps, int(relu), _p(amax), _p(_state.PREDICATE), _stream())
+        if amax is not None:
+            tag_amax(out, amax)
+        ctx.save_for_backward(y, out if relu else None, mean, rstd, gamma)
+        ctx.relu, ctx.groups = relu, groups
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, out, mean, rstd, gamma = ctx.saved_tensors
+        B, H, W, C = y.shape
+        dev = y.device
+        dout = dout.contiguous()
+        dx = torch.empty_like(y)
+        dg = torch.empty(C, device=dev, dtype=torch.float32) if ctx.needs_input_grad[2] else None
+        db = torch.empty(C, device=dev, dtype=torch.float32) if ctx.needs_input_grad[3] else None
+        amax = amax_slot(dev) if _state.CONV_MODE == "f16x2" else None
+        ws = torch.empty(query("onda_gn_site_ws", B, H * W, C), device=dev, dtype=torch.float32)
+        call("onda_gn_site_bwd", _p(dout), _p(out), _p(y), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db), _p(ws),
+             B, H * W, C, ctx.groups, int(ctx.relu), _p(amax), _stream())
+        if amax is not None:
+            tag_amax(dx, amax)  # dx is the dy of the conv below: data gradient and weight gradient read it
+        return dx, None, dg, db, None, None, None
+
+
 
 
 class SEScaleFn(torch.autograd.Function):
