@@ -1,4 +1,5 @@
-// HBM-bound normalisation kernels: BatchNorm2d (batch / running statistics), GroupNorm,
+// HBM-bound normalisation kernels: BatchNorm2d (batch / running statistics), GroupNorm (one family of kernels --
+// gn_finalize / gn_apply / GnBwdRed / gn_bwd_group / gn_bwd_apply -- for the ASPP head and for the backbone convolutions),
 // per-image column sums (SE pooling, bias gradients).  NHWC rows, 16-byte accesses, two-stage
 // fixed-order reductions (block partials -> finalize) so results are bitwise reproducible.
 #include "common.h"
@@ -75,6 +76,48 @@ static int launch_colreduce(const F& f, int B, int64_t HW, int C, float* partial
 
 #define LD4(p) (*reinterpret_cast<const f32x4*>(p))
 
+// ---- steps every family takes, written once -------------------------------------------------
+// The gradient behind a ReLU: g where the forward output is positive, 0 elsewhere.
+__device__ __forceinline__ f32x4 relu_mask(f32x4 g, const f32x4 ov) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) g[j] = ov[j] > 0.f ? g[j] : 0.f;
+  return g;
+}
+
+// Running max|v| of an apply pass (folded into the tensor's slots by amax_update_block at the end of the kernel).
+__device__ __forceinline__ float max_abs4(float mx, const f32x4 v) {
+  return fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+}
+
+// One-pass statistics finished in double: sum, sum of squares over `count` values.
+struct Moments {
+  double mean, var, rstd;
+};
+__device__ __forceinline__ Moments moments(double s1, double s2, double count, float eps) {
+  Moments m;
+  m.mean = s1 / count;
+  m.var = s2 / count - m.mean * m.mean;
+  if (m.var < 0.0) m.var = 0.0;
+  m.rstd = 1.0 / sqrt(m.var + (double)eps);
+  return m;
+}
+
+// One wave sums column `ch` of image b's rows of a [b][rows][2][C] partial table in double: lanes stride over the rows, then
+// the wave reduction.  PAIR false: the first of the two sums only (s2 stays 0, its load is not made).
+template <bool PAIR>
+__device__ __forceinline__ void table_column(const float* __restrict__ partials, int rows, int b, int C, int ch, double& s1,
+                                             double& s2) {
+  s1 = 0.0;
+  s2 = 0.0;
+  for (int k = threadIdx.x & 63; k < rows; k += 64) {
+    const size_t base = (((size_t)b * rows + k) * 2) * C + ch;
+    s1 += (double)partials[base];
+    if (PAIR) s2 += (double)partials[base + C];
+  }
+  s1 = wave_sum_d(s1);
+  if (PAIR) s2 = wave_sum_d(s2);
+}
+
 struct SqStats {  // a = x, b = x*x
   const float* x;
   int64_t HW;
@@ -108,11 +151,7 @@ struct BnBwdRed {  // g = dout*(out>0); a = g, b = g*xhat; optional dres = g
   __device__ void operator()(int, int64_t r, int col, f32x4& a, f32x4& bb) const {
     const size_t o = (size_t)r * C + col;
     f32x4 g = LD4(dout + o);
-    if (relu) {
-      const f32x4 ov = LD4(out + o);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) g[j] = ov[j] > 0.f ? g[j] : 0.f;
-    }
+    if (relu) g = relu_mask(g, LD4(out + o));
     if (dres) *reinterpret_cast<f32x4*>(dres + o) = g;
     const f32x4 xh = (LD4(x + o) - LD4(mean + col)) * LD4(invstd + col);
     a = g;
@@ -120,7 +159,19 @@ struct BnBwdRed {  // g = dout*(out>0); a = g, b = g*xhat; optional dres = g
   }
 };
 
-struct GnBwdRed {
+// The GroupNorm statistics of the 4 columns from `col` of image b: one group (a multiple of 4 channels per group: g1 == g0)
+// or two (2 channels per group, the stem: columns col + 2, col + 3 lie in the next group).
+struct GnQuad {
+  int g0, g1;
+  __device__ GnQuad(int b, int groups, int cpg, int col) : g0(b * groups + col / cpg), g1(cpg == 2 ? g0 + 1 : g0) {}
+  // entry `k` of a per-(image, group) table of `n` floats a group: mean / rstd [B][groups], gsum [B][groups][2]
+  __device__ f32x4 of(const float* __restrict__ t, int n = 1, int k = 0) const {
+    const float v0 = t[g0 * n + k], v1 = t[g1 * n + k];
+    return f32x4{v0, v0, v1, v1};
+  }
+};
+
+struct GnBwdRed {  // g = dout*(out>0)*chmul; a = g, b = g*xhat
   const float* dout;
   const float* out;
   const float* x;
@@ -132,17 +183,11 @@ struct GnBwdRed {
   __device__ void operator()(int b, int64_t r, int col, f32x4& a, f32x4& bb) const {
     const size_t row = (size_t)b * HW + r;
     f32x4 g = LD4(dout + row * lddo + col);
-    if (relu) {
-      const f32x4 ov = LD4(out + row * ldo + col);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) g[j] = ov[j] > 0.f ? g[j] : 0.f;
-    }
+    if (relu) g = relu_mask(g, LD4(out + row * ldo + col));
     if (chmul) g *= LD4(chmul + (size_t)b * C + col);
-    const int grp = col / (C / groups);  // the 4 columns share a group (C/groups is a multiple of 4)
-    const float mu = mean[b * groups + grp], rs = rstd[b * groups + grp];
-    const f32x4 xh = (LD4(x + row * ldx + col) - mu) * rs;
+    const GnQuad q(b, groups, C / groups, col);
     a = g;
-    bb = g * xh;
+    bb = g * ((LD4(x + row * ldx + col) - q.of(mean)) * q.of(rstd));
   }
 };
 
@@ -151,26 +196,18 @@ struct GnBwdRed {
 __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ partials, int tiles, int C,
                                                           double count, float eps, float* mean, float* invstd,
                                                           float* rmean, float* rvar, int64_t* nbt, float momentum) {
-  const int lane = threadIdx.x & 63;
   const int ch = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (blockIdx.x == 0 && threadIdx.x == 0 && nbt) *nbt += 1;
   if (ch >= C) return;
-  double s1 = 0.0, s2 = 0.0;
-  for (int tl = lane; tl < tiles; tl += 64) {
-    s1 += (double)partials[((size_t)tl * 2 + 0) * C + ch];
-    s2 += (double)partials[((size_t)tl * 2 + 1) * C + ch];
-  }
-  s1 = wave_sum_d(s1);
-  s2 = wave_sum_d(s2);
-  if (lane != 0) return;
-  const double mu = s1 / count;
-  double var = s2 / count - mu * mu;
-  if (var < 0.0) var = 0.0;
-  mean[ch] = (float)mu;
-  invstd[ch] = (float)(1.0 / sqrt(var + (double)eps));
+  double s1, s2;
+  table_column<true>(partials, tiles, 0, C, ch, s1, s2);
+  if ((threadIdx.x & 63) != 0) return;
+  const Moments m = moments(s1, s2, count, eps);
+  mean[ch] = (float)m.mean;
+  invstd[ch] = (float)m.rstd;
   if (rmean) {
-    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    rmean[ch] = (1.f - momentum) * rmean[ch] + momentum * (float)mu;
+    const double unbiased = count > 1.0 ? m.var * count / (count - 1.0) : m.var;
+    rmean[ch] = (1.f - momentum) * rmean[ch] + momentum * (float)m.mean;
     rvar[ch] = (1.f - momentum) * rvar[ch] + momentum * (float)unbiased;
   }
 }
@@ -192,7 +229,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
       for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
     }
     *reinterpret_cast<f32x4*>(out + e * 4) = v;
-    mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    mx = max_abs4(mx, v);
   }
   __shared__ float amax_red[4];
   if (amax != nullptr) amax_update_block(amax, mx, amax_red);
@@ -208,21 +245,17 @@ __global__ void bn_fold_kernel(const float* gamma, const float* beta, const floa
   shift[ch] = beta[ch] - rmean[ch] * sc;
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_sums_kernel(const float* __restrict__ partials, int chunks, int C,
-                                                          float* sums) {
-  const int lane = threadIdx.x & 63;
-  const int ch = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (ch >= C) return;
-  double s1 = 0.0, s2 = 0.0;
-  for (int k = lane; k < chunks; k += 64) {
-    s1 += (double)partials[((size_t)k * 2 + 0) * C + ch];
-    s2 += (double)partials[((size_t)k * 2 + 1) * C + ch];
-  }
-  s1 = wave_sum_d(s1);
-  s2 = wave_sum_d(s2);
-  if (lane == 0) {
-    sums[ch] = (float)s1;
-    sums[C + ch] = (float)s2;
+// partials[b][chunk][2][C] -> AB[b][2][C] (one wave per (b,c)); with B = 1 the two sums of the BatchNorm backward
+__global__ __launch_bounds__(256) void pair_finalize_kernel(const float* __restrict__ partials, int chunks, int B,
+                                                            int C, float* __restrict__ AB) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= B * C) return;
+  const int b = i / C, ch = i % C;
+  double s1, s2;
+  table_column<true>(partials, chunks, b, C, ch, s1, s2);
+  if ((threadIdx.x & 63) == 0) {
+    AB[((size_t)b * 2 + 0) * C + ch] = (float)s1;
+    AB[((size_t)b * 2 + 1) * C + ch] = (float)s2;
   }
 }
 
@@ -239,35 +272,39 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total4; e += (size_t)gridDim.x * blockDim.x) {
     const int col = (int)(e % c4) * 4;
     f32x4 g = LD4(dout + e * 4);
-    if (relu) {
-      const f32x4 ov = LD4(out + e * 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) g[j] = ov[j] > 0.f ? g[j] : 0.f;
-    }
+    if (relu) g = relu_mask(g, LD4(out + e * 4));
     const f32x4 is = LD4(invstd + col);
     const f32x4 xh = (LD4(x + e * 4) - LD4(mean + col)) * is;
     const f32x4 v = LD4(gamma + col) * is * (g - LD4(sums + col) * inv_m - xh * (LD4(sums + C + col) * inv_m));
     *reinterpret_cast<f32x4*>(dx + e * 4) = v;
-    mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    mx = max_abs4(mx, v);
   }
   __shared__ float amax_red[4];
   if (amax != nullptr) amax_update_block(amax, mx, amax_red);
 }
 
 // ---- GroupNorm --------------------------------------------------------------------------
-// One workgroup per (image, group): 256 threads stride over chunks x channels-of-the-group, waves combined in fixed order
-// (one wave per pair walked 16+ dependent iterations: 17 us for 30 KB).
-__global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ partials, int chunks, int B,
+// One family for the ASPP head (row strides: the concat buffer; a per-(image, channel) multiplier; a multiple of 4 channels
+// per group) and for a backbone convolution -- the stem and the four shortcuts of DeepLabv2-Resnet50-GN (dense rows; 2
+// channels per group at the stem; a device predicate on every forward launch; max|dx| left behind as well).  Statistics from
+// the reduction pass or from a conv epilogue's tile partials.
+//
+// Finalize, one workgroup per (image, group): 256 threads stride over rows x channels-of-the-group, waves combined in fixed
+// order (one wave per pair walked 16+ dependent iterations: 17 us for 30 KB).  Image b owns rows [b * rows, (b + 1) * rows) of
+// `row_stride` floats each, the sums in the first C of them and the sums of squares in the next C: [b][chunk][2][C] of
+// colreduce_kernel, [tile][stat_rows][C] of a conv epilogue whose tiles do not straddle two images.
+__global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ partials, int rows, int64_t row_stride,
                                                           int C, int groups, double count, float eps, float* mean,
-                                                          float* rstd) {
+                                                          float* rstd, const int32_t* run_if) {
+  if (run_if != nullptr && *run_if == 0) return;
   __shared__ double red[2][4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int idx = blockIdx.x;
   const int b = idx / groups, g = idx % groups, cpg = C / groups;
   double s1 = 0.0, s2 = 0.0;
-  for (int i = threadIdx.x; i < chunks * cpg; i += 256) {
+  for (int i = threadIdx.x; i < rows * cpg; i += 256) {
     const int k = i / cpg, j = i - k * cpg;
-    const size_t base = (((size_t)b * chunks + k) * 2) * C + g * cpg + j;
+    const size_t base = ((size_t)b * rows + k) * row_stride + g * cpg + j;
     s1 += (double)partials[base];
     s2 += (double)partials[base + C];
   }
@@ -281,57 +318,39 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
   if (threadIdx.x != 0) return;
   s1 = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
   s2 = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-  const double mu = s1 / count;
-  double var = s2 / count - mu * mu;
-  if (var < 0.0) var = 0.0;
-  mean[idx] = (float)mu;
-  rstd[idx] = (float)(1.0 / sqrt(var + (double)eps));
+  const Moments m = moments(s1, s2, count, eps);
+  mean[idx] = (float)m.mean;
+  rstd[idx] = (float)m.rstd;
 }
 
+// out = relu((x - mu) * rs * gamma + beta) * chmul; rows of ldx / ldo floats; chmul [B][C], amax and run_if may be null
 __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__ x, int ldx,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        const float* __restrict__ chmul, float* __restrict__ out,
                                                        int ldo, const float* __restrict__ mean,
                                                        const float* __restrict__ rstd, int64_t HW, int C, int groups,
-                                                       size_t total4, int relu, float* __restrict__ amax) {
+                                                       size_t total4, int relu, float* __restrict__ amax,
+                                                       const int32_t* run_if) {
+  if (run_if != nullptr && *run_if == 0) return;
   const int c4 = C / 4, cpg = C / groups;
   float mx = 0.f;
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total4; e += (size_t)gridDim.x * blockDim.x) {
     const int col = (int)(e % c4) * 4;
     const size_t row = e / c4;
     const int b = (int)(row / HW);
-    const int gi = b * groups + col / cpg;
-    f32x4 v = (LD4(x + row * ldx + col) - mean[gi]) * rstd[gi] * LD4(gamma + col) + LD4(beta + col);
+    const GnQuad q(b, groups, cpg, col);
+    f32x4 v = (LD4(x + row * ldx + col) - q.of(mean)) * q.of(rstd) * LD4(gamma + col) + LD4(beta + col);
     if (relu) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
     }
     if (chmul) v *= LD4(chmul + (size_t)b * C + col);
     *reinterpret_cast<f32x4*>(out + row * ldo + col) = v;
-    mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    mx = max_abs4(mx, v);
   }
-  if (amax != nullptr) amax_update(amax, mx);  // the output feeds a convolution (directly, or through the SE gate): leave max|out| behind
-}
-
-// partials[b][chunk][2][C] -> AB[b][2][C] (one wave per (b,c))
-__global__ __launch_bounds__(256) void pair_finalize_kernel(const float* __restrict__ partials, int chunks, int B,
-                                                            int C, float* __restrict__ AB) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= B * C) return;
-  const int b = i / C, ch = i % C;
-  double s1 = 0.0, s2 = 0.0;
-  for (int k = lane; k < chunks; k += 64) {
-    const size_t base = (((size_t)b * chunks + k) * 2) * C + ch;
-    s1 += (double)partials[base];
-    s2 += (double)partials[base + C];
-  }
-  s1 = wave_sum_d(s1);
-  s2 = wave_sum_d(s2);
-  if (lane == 0) {
-    AB[((size_t)b * 2 + 0) * C + ch] = (float)s1;
-    AB[((size_t)b * 2 + 1) * C + ch] = (float)s2;
-  }
+  // the output feeds a convolution (directly, or through the SE gate): leave max|out| behind
+  __shared__ float amax_red[4];
+  if (amax != nullptr) amax_update_block(amax, mx, amax_red);
 }
 
 // AB[b][2][C] -> dgamma/dbeta and the per-(image, group) sums the dx formula needs
@@ -361,6 +380,7 @@ __global__ void gn_bwd_group_kernel(const float* __restrict__ AB, int B, int C, 
   }
 }
 
+// g = dout * (out > 0) * chmul; dx = rs * (gamma * g - (ds + xhat * dq) / n), dense rows of C floats; amax may be null
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restrict__ dout, int lddo,
                                                            const float* __restrict__ out, int ldo,
                                                            const float* __restrict__ x, int ldx,
@@ -370,155 +390,22 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
                                                            const float* __restrict__ rstd,
                                                            const float* __restrict__ gsum, float* __restrict__ dx,
                                                            int64_t HW, int C, int groups, size_t total4, float inv_n,
-                                                           int relu) {
+                                                           int relu, float* __restrict__ amax) {
   const int c4 = C / 4, cpg = C / groups;
+  float mx = 0.f;
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total4; e += (size_t)gridDim.x * blockDim.x) {
     const int col = (int)(e % c4) * 4;
     const size_t row = e / c4;
     const int b = (int)(row / HW);
-    const int gi = b * groups + col / cpg;
     f32x4 g = LD4(dout + row * lddo + col);
-    if (relu) {
-      const f32x4 ov = LD4(out + row * ldo + col);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) g[j] = ov[j] > 0.f ? g[j] : 0.f;
-    }
+    if (relu) g = relu_mask(g, LD4(out + row * ldo + col));
     if (chmul) g *= LD4(chmul + (size_t)b * C + col);
-    const float rs = rstd[gi];
-    const f32x4 xh = (LD4(x + row * ldx + col) - mean[gi]) * rs;
-    const f32x4 v = rs * (LD4(gamma + col) * g - (gsum[gi * 2] + xh * gsum[gi * 2 + 1]) * inv_n);
-    *reinterpret_cast<f32x4*>(dx + row * C + col) = v;
-  }
-}
-
-// ---- GroupNorm on a backbone convolution ------------------------------------------------------
-// The stem and the four shortcuts of DeepLabv2-Resnet50-GN: dense [B][HW][C] rows, 2 channels per group (the stem: one f32x4
-// spans two groups) or a multiple of 4.  Statistics from the reduction pass or from the conv epilogue's tile partials; a
-// device predicate on every forward launch; max|out| / max|dx| left behind for the convolutions on either side.
-__device__ __forceinline__ void gn_site_stats(const float* __restrict__ mean, const float* __restrict__ rstd, int b,
-                                              int groups, int cpg, int col, f32x4& mu, f32x4& rs) {
-  const int g0 = b * groups + col / cpg;
-  const int g1 = cpg == 2 ? g0 + 1 : g0;  // columns col + 2, col + 3
-  const float m0 = mean[g0], m1 = mean[g1], r0 = rstd[g0], r1 = rstd[g1];
-  mu = f32x4{m0, m0, m1, m1};
-  rs = f32x4{r0, r0, r1, r1};
-}
-
-// gn_finalize_kernel over either table: image b owns rows [b * rows, (b + 1) * rows) of `row_stride` floats each, the sums in
-// the first C of them and the sums of squares in the next C ([b][chunk][2][C] of colreduce_kernel, [tile][stat_rows][C] of a
-// conv epilogue whose tiles do not straddle two images).
-__global__ __launch_bounds__(256) void gn_site_finalize_kernel(const float* __restrict__ partials, int rows,
-                                                               int64_t row_stride, int C, int groups, double count,
-                                                               float eps, float* mean, float* rstd,
-                                                               const int32_t* run_if) {
-  if (run_if != nullptr && *run_if == 0) return;
-  __shared__ double red[2][4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int idx = blockIdx.x;
-  const int b = idx / groups, g = idx % groups, cpg = C / groups;
-  double s1 = 0.0, s2 = 0.0;
-  for (int i = threadIdx.x; i < rows * cpg; i += 256) {
-    const int k = i / cpg, j = i - k * cpg;
-    const size_t base = ((size_t)b * rows + k) * row_stride + g * cpg + j;
-    s1 += (double)partials[base];
-    s2 += (double)partials[base + C];
-  }
-  s1 = wave_sum_d(s1);
-  s2 = wave_sum_d(s2);
-  if (lane == 0) {
-    red[0][wave] = s1;
-    red[1][wave] = s2;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  s1 = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-  s2 = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
-  const double mu = s1 / count;
-  double var = s2 / count - mu * mu;
-  if (var < 0.0) var = 0.0;
-  mean[idx] = (float)mu;
-  rstd[idx] = (float)(1.0 / sqrt(var + (double)eps));
-}
-
-__global__ __launch_bounds__(256) void gn_site_apply_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, float* __restrict__ out,
-                                                            const float* __restrict__ mean,
-                                                            const float* __restrict__ rstd, int64_t HW, int C, int groups,
-                                                            size_t total4, int relu, float* __restrict__ amax,
-                                                            const int32_t* run_if) {
-  if (run_if != nullptr && *run_if == 0) return;
-  const int c4 = C / 4, cpg = C / groups;
-  float mx = 0.f;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total4; e += (size_t)gridDim.x * blockDim.x) {
-    const int col = (int)(e % c4) * 4;
-    const int b = (int)(e / c4 / HW);
-    f32x4 mu, rs;
-    gn_site_stats(mean, rstd, b, groups, cpg, col, mu, rs);
-    f32x4 v = (LD4(x + e * 4) - mu) * rs * LD4(gamma + col) + LD4(beta + col);
-    if (relu) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-    }
-    *reinterpret_cast<f32x4*>(out + e * 4) = v;
-    mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
-  }
-  __shared__ float amax_red[4];
-  if (amax != nullptr) amax_update_block(amax, mx, amax_red);
-}
-
-struct GnSiteBwdRed {  // g = dout*(out>0); a = g, b = g*xhat
-  const float* dout;
-  const float* out;
-  const float* x;
-  const float* mean;
-  const float* rstd;
-  int64_t HW;
-  int C, groups, relu;
-  __device__ void operator()(int b, int64_t r, int col, f32x4& a, f32x4& bb) const {
-    const size_t o = ((size_t)b * HW + r) * C + col;
-    f32x4 g = LD4(dout + o);
-    if (relu) {
-      const f32x4 ov = LD4(out + o);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) g[j] = ov[j] > 0.f ? g[j] : 0.f;
-    }
-    f32x4 mu, rs;
-    gn_site_stats(mean, rstd, b, groups, C / groups, col, mu, rs);
-    a = g;
-    bb = g * ((LD4(x + o) - mu) * rs);
-  }
-};
-
-__global__ __launch_bounds__(256) void gn_site_bwd_apply_kernel(const float* __restrict__ dout,
-                                                                const float* __restrict__ out,
-                                                                const float* __restrict__ x,
-                                                                const float* __restrict__ gamma,
-                                                                const float* __restrict__ mean,
-                                                                const float* __restrict__ rstd,
-                                                                const float* __restrict__ gsum, float* __restrict__ dx,
-                                                                int64_t HW, int C, int groups, size_t total4, float inv_n,
-                                                                int relu, float* __restrict__ amax) {
-  const int c4 = C / 4, cpg = C / groups;
-  float mx = 0.f;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total4; e += (size_t)gridDim.x * blockDim.x) {
-    const int col = (int)(e % c4) * 4;
-    const int b = (int)(e / c4 / HW);
-    f32x4 g = LD4(dout + e * 4);
-    if (relu) {
-      const f32x4 ov = LD4(out + e * 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) g[j] = ov[j] > 0.f ? g[j] : 0.f;
-    }
-    f32x4 mu, rs;
-    gn_site_stats(mean, rstd, b, groups, cpg, col, mu, rs);
-    const int g0 = b * groups + col / cpg;
-    const int g1 = cpg == 2 ? g0 + 1 : g0;
-    const f32x4 ds = {gsum[g0 * 2], gsum[g0 * 2], gsum[g1 * 2], gsum[g1 * 2]};
-    const f32x4 dq = {gsum[g0 * 2 + 1], gsum[g0 * 2 + 1], gsum[g1 * 2 + 1], gsum[g1 * 2 + 1]};
-    const f32x4 xh = (LD4(x + e * 4) - mu) * rs;
-    const f32x4 v = rs * (LD4(gamma + col) * g - (ds + xh * dq) * inv_n);
+    const GnQuad q(b, groups, cpg, col);
+    const f32x4 rs = q.of(rstd);
+    const f32x4 xh = (LD4(x + row * ldx + col) - q.of(mean)) * rs;
+    const f32x4 v = rs * (LD4(gamma + col) * g - (q.of(gsum, 2, 0) + xh * q.of(gsum, 2, 1)) * inv_n);
     *reinterpret_cast<f32x4*>(dx + e * 4) = v;
-    mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    mx = max_abs4(mx, v);
   }
   __shared__ float amax_red[4];
   if (amax != nullptr) amax_update_block(amax, mx, amax_red);
@@ -526,14 +413,11 @@ __global__ __launch_bounds__(256) void gn_site_bwd_apply_kernel(const float* __r
 
 __global__ __launch_bounds__(256) void colsum_finalize_kernel(const float* __restrict__ partials, int chunks, int B,
                                                               int C, float alpha, float* out) {
-  const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= B * C) return;
-  const int b = i / C, ch = i % C;
-  double s = 0.0;
-  for (int k = lane; k < chunks; k += 64) s += (double)partials[(((size_t)b * chunks + k) * 2) * C + ch];
-  s = wave_sum_d(s);
-  if (lane == 0) out[i] = (float)(s * (double)alpha);
+  double s, unused;
+  table_column<false>(partials, chunks, i / C, C, i % C, s, unused);
+  if ((threadIdx.x & 63) == 0) out[i] = (float)(s * (double)alpha);
 }
 
 static inline unsigned ew_grid(size_t total4) {
@@ -594,7 +478,7 @@ int onda_bn_bwd(const float* dout, const float* out, const float* x, const float
   BnBwdRed f{dout, out, x, mean, invstd, dres, C, relu};
   int rc = launch_colreduce(f, 1, M, C, ws, p, ONDA_STREAM(s));
   if (rc) return rc;
-  hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3((C + 3) / 4), dim3(256), 0, ONDA_STREAM(s), ws, p.chunks, C, sums);
+  hipLaunchKernelGGL(pair_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, ONDA_STREAM(s), ws, p.chunks, 1, C, sums);
   const size_t total4 = (size_t)M * C / 4;
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, ONDA_STREAM(s), dout, out, x, mean,
                      invstd, gamma, sums, dx, total4, C, (float)(1.0 / (double)M), relu, amax);
@@ -606,21 +490,53 @@ int64_t onda_gn_ws(int B, int64_t HW, int C) {
   return (int64_t)B * p.chunks * 2 * C + (int64_t)B * C * 2 + (int64_t)B * 2 * 128 + 64;
 }
 
+// The forward launches of both GroupNorm entry points.  Statistics: `rows` partial rows an image of `row_stride` floats in
+// `stats`, or (stats == nullptr) the reduction pass over x into ws.  Then finalize and the apply pass.
+static int gn_forward(const float* x, int ldx, const float* stats, int rows, int64_t row_stride, const float* gamma,
+                      const float* beta, const float* chmul, float* out, int ldo, float* mean, float* rstd, float* ws, int B,
+                      int64_t HW, int C, int groups, float eps, int relu, float* amax, const int32_t* run_if, hipStream_t s) {
+  if (stats == nullptr) {
+    const ColPlan p = col_plan(B, HW, C);
+    SqStats f{x, HW, ldx};
+    int rc = launch_colreduce(f, B, HW, C, ws, p, s, run_if);
+    if (rc) return rc;
+    stats = ws;
+    rows = p.chunks;
+    row_stride = (int64_t)2 * C;
+  }
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3(B * groups), dim3(256), 0, s, stats, rows, row_stride, C, groups,
+                     (double)HW * (C / groups), eps, mean, rstd, run_if);
+  const size_t total4 = (size_t)B * HW * C / 4;
+  hipLaunchKernelGGL(gn_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, s, x, ldx, gamma, beta, chmul, out, ldo, mean, rstd,
+                     HW, C, groups, total4, relu, amax, run_if);
+  return ONDA_LAUNCH_RESULT();
+}
+
+// The backward launches of both: ws = partials [B][chunks][2][C], AB [B][2][C], gsum [B][groups][2].
+static int gn_backward(const float* dout, int lddo, const float* out, int ldo, const float* x, int ldx, const float* gamma,
+                       const float* chmul, const float* mean, const float* rstd, float* dx, float* dgamma, float* dbeta,
+                       float* ws, int B, int64_t HW, int C, int groups, int relu, float* amax, hipStream_t s) {
+  const ColPlan p = col_plan(B, HW, C);
+  float* AB = ws + (size_t)B * p.chunks * 2 * C;
+  float* gsum = AB + (size_t)B * 2 * C;
+  GnBwdRed f{dout, out, x, chmul, mean, rstd, HW, lddo, ldo, ldx, C, groups, relu};
+  int rc = launch_colreduce(f, B, HW, C, ws, p, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(pair_finalize_kernel, dim3((B * C + 3) / 4), dim3(256), 0, s, ws, p.chunks, B, C, AB);
+  hipLaunchKernelGGL(gn_bwd_group_kernel, dim3(1), dim3(256), 0, s, AB, B, C, groups, gamma, dgamma, dbeta, gsum);
+  const size_t total4 = (size_t)B * HW * C / 4;
+  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, s, dout, lddo, out, ldo, x, ldx, gamma, chmul,
+                     mean, rstd, gsum, dx, HW, C, groups, total4, (float)(1.0 / ((double)HW * (C / groups))), relu, amax);
+  return ONDA_LAUNCH_RESULT();
+}
+
 int onda_gn_fwd(const float* x, int ldx, const float* gamma, const float* beta, const float* chmul, float* out, int ldo,
                 float* mean, float* rstd, float* ws, int B, int64_t HW, int C, int groups, float eps, int relu, float* amax,
                 onda_stream_t s) {
   ONDA_REQUIRE(x && gamma && beta && out && mean && rstd && ws);
   ONDA_REQUIRE(C % groups == 0 && (C / groups) % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0);
-  const ColPlan p = col_plan(B, HW, C);
-  SqStats f{x, HW, ldx};
-  int rc = launch_colreduce(f, B, HW, C, ws, p, ONDA_STREAM(s));
-  if (rc) return rc;
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(B * groups), dim3(256), 0, ONDA_STREAM(s), ws, p.chunks, B,
-                     C, groups, (double)HW * (C / groups), eps, mean, rstd);
-  const size_t total4 = (size_t)B * HW * C / 4;
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, ONDA_STREAM(s), x, ldx, gamma, beta, chmul,
-                     out, ldo, mean, rstd, HW, C, groups, total4, relu, amax);
-  return ONDA_LAUNCH_RESULT();
+  return gn_forward(x, ldx, nullptr, 0, 0, gamma, beta, chmul, out, ldo, mean, rstd, ws, B, HW, C, groups, eps, relu, amax,
+                    nullptr, ONDA_STREAM(s));
 }
 
 int onda_gn_bwd(const float* dout, int lddo, const float* out, int ldo, const float* x, int ldx, const float* gamma,
@@ -628,22 +544,11 @@ int onda_gn_bwd(const float* dout, int lddo, const float* out, int ldo, const fl
                 float* ws, int B, int64_t HW, int C, int groups, int relu, onda_stream_t s) {
   ONDA_REQUIRE(dout && x && gamma && mean && rstd && dx && ws && (!relu || out));
   ONDA_REQUIRE(C % groups == 0 && (C / groups) % 4 == 0 && ldx % 4 == 0 && lddo % 4 == 0);
-  const ColPlan p = col_plan(B, HW, C);
-  float* AB = ws + (size_t)B * p.chunks * 2 * C;
-  float* gsum = AB + (size_t)B * 2 * C;
-  GnBwdRed f{dout, out, x, chmul, mean, rstd, HW, lddo, ldo, ldx, C, groups, relu};
-  int rc = launch_colreduce(f, B, HW, C, ws, p, ONDA_STREAM(s));
-  if (rc) return rc;
-  hipLaunchKernelGGL(pair_finalize_kernel, dim3((B * C + 3) / 4), dim3(256), 0, ONDA_STREAM(s), ws, p.chunks, B, C, AB);
-  hipLaunchKernelGGL(gn_bwd_group_kernel, dim3(1), dim3(256), 0, ONDA_STREAM(s), AB, B, C, groups, gamma, dgamma, dbeta,
-                     gsum);
-  const size_t total4 = (size_t)B * HW * C / 4;
-  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, ONDA_STREAM(s), dout, lddo, out, ldo, x,
-                     ldx, gamma, chmul, mean, rstd, gsum, dx, HW, C, groups, total4,
-                     (float)(1.0 / ((double)HW * (C / groups))), relu);
-  return ONDA_LAUNCH_RESULT();
+  return gn_backward(dout, lddo, out, ldo, x, ldx, gamma, chmul, mean, rstd, dx, dgamma, dbeta, ws, B, HW, C, groups, relu,
+                     nullptr, ONDA_STREAM(s));
 }
 
+// A backbone convolution's GroupNorm: dense [B][HW][C] rows, 2 channels per group or a multiple of 4.
 static inline bool gn_site_shape_ok(int B, int64_t HW, int C, int groups) {
   if (B < 1 || HW < 1 || C < 4 || groups < 1 || C % 4 != 0 || C % groups != 0) return false;
   const int cpg = C / groups;
@@ -660,26 +565,17 @@ int onda_gn_site_fwd(const float* x, const float* stats, int tiles, int stat_row
                      float eps, int relu, float* amax, const int32_t* run_if, onda_stream_t s) {
   ONDA_REQUIRE(x && gamma && beta && out && mean && rstd && gn_site_shape_ok(B, HW, C, groups));
   if (!ONDA_ALIGNED16(x) || !ONDA_ALIGNED16(out) || !ONDA_ALIGNED16(gamma) || !ONDA_ALIGNED16(beta)) return ONDA_EALIGN;
-  const double count = (double)HW * (C / groups);
+  int rows = 0;
   if (stats != nullptr) {
     // one partial row per tile row and no tile across two images (a stream-K remainder appends rows: not taken)
     ONDA_REQUIRE((stat_rows == 2 || stat_rows == 4) && tile_rows > 0 && HW % tile_rows == 0 &&
                  (int64_t)tiles == (int64_t)B * (HW / tile_rows));
-    hipLaunchKernelGGL(gn_site_finalize_kernel, dim3(B * groups), dim3(256), 0, ONDA_STREAM(s), stats,
-                       (int)(HW / tile_rows), (int64_t)stat_rows * C, C, groups, count, eps, mean, rstd, run_if);
+    rows = (int)(HW / tile_rows);
   } else {
     ONDA_REQUIRE(ws != nullptr);
-    const ColPlan p = col_plan(B, HW, C);
-    SqStats f{x, HW, C};
-    int rc = launch_colreduce(f, B, HW, C, ws, p, ONDA_STREAM(s), run_if);
-    if (rc) return rc;
-    hipLaunchKernelGGL(gn_site_finalize_kernel, dim3(B * groups), dim3(256), 0, ONDA_STREAM(s), ws, p.chunks,
-                       (int64_t)2 * C, C, groups, count, eps, mean, rstd, run_if);
   }
-  const size_t total4 = (size_t)B * HW * C / 4;
-  hipLaunchKernelGGL(gn_site_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, ONDA_STREAM(s), x, gamma, beta, out, mean,
-                     rstd, HW, C, groups, total4, relu, amax, run_if);
-  return ONDA_LAUNCH_RESULT();
+  return gn_forward(x, C, stats, rows, (int64_t)stat_rows * C, gamma, beta, nullptr, out, C, mean, rstd, ws, B, HW, C, groups,
+                    eps, relu, amax, run_if, ONDA_STREAM(s));
 }
 
 int onda_gn_site_bwd(const float* dout, const float* out, const float* x, const float* gamma, const float* mean,
@@ -689,19 +585,8 @@ int onda_gn_site_bwd(const float* dout, const float* out, const float* x, const 
   if (!ONDA_ALIGNED16(dout) || !ONDA_ALIGNED16(x) || !ONDA_ALIGNED16(dx) || !ONDA_ALIGNED16(gamma) ||
       (relu && !ONDA_ALIGNED16(out)))
     return ONDA_EALIGN;
-  const ColPlan p = col_plan(B, HW, C);
-  float* AB = ws + (size_t)B * p.chunks * 2 * C;
-  float* gsum = AB + (size_t)B * 2 * C;
-  GnSiteBwdRed f{dout, out, x, mean, rstd, HW, C, groups, relu};
-  int rc = launch_colreduce(f, B, HW, C, ws, p, ONDA_STREAM(s));
-  if (rc) return rc;
-  hipLaunchKernelGGL(pair_finalize_kernel, dim3((B * C + 3) / 4), dim3(256), 0, ONDA_STREAM(s), ws, p.chunks, B, C, AB);
-  hipLaunchKernelGGL(gn_bwd_group_kernel, dim3(1), dim3(256), 0, ONDA_STREAM(s), AB, B, C, groups, gamma, dgamma, dbeta,
-                     gsum);
-  const size_t total4 = (size_t)B * HW * C / 4;
-  hipLaunchKernelGGL(gn_site_bwd_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, ONDA_STREAM(s), dout, out, x, gamma,
-                     mean, rstd, gsum, dx, HW, C, groups, total4, (float)(1.0 / ((double)HW * (C / groups))), relu, amax);
-  return ONDA_LAUNCH_RESULT();
+  return gn_backward(dout, C, out, C, x, C, gamma, nullptr, mean, rstd, dx, dgamma, dbeta, ws, B, HW, C, groups, relu, amax,
+                     ONDA_STREAM(s));
 }
 
 int64_t onda_colsum_ws(int B, int64_t HW, int C) {

@@ -98,10 +98,6 @@ class BNTrainFn(torch.autograd.Function):
         return dx, None, None, None, dres, None, None, None
 
 
-
-
-
-
 class BNTrainLimbFn(torch.autograd.Function):
     """BNTrainFn whose output exists as limb planes only ("f16x2" / "dma"): the output of a train-mode BatchNorm
     (+residual, +ReLU) is consumed by convolutions, a later residual add and its own backward mask -- all of which
@@ -343,8 +339,6 @@ class GNSiteFn(torch.autograd.Function):
         if amax is not None:
             tag_amax(dx, amax)  # dx is the dy of the conv below: data gradient and weight gradient read it
         return dx, None, dg, db, None, None, None
-
-
 
 
 class SEScaleFn(torch.autograd.Function):

@@ -5,6 +5,9 @@
     from the reduction pass over the conv output (ops.GN_FUSED_STATS on / off), forward and backward;
   * one shortcut site (layer1.0.downsample: 4 x 129 x 257 x 256).  129 x 257 = 33153 rows per image is no multiple of a tile's
     rows, so only the reduction pass is legal there -- as at the other three shortcuts (65 x 129) at this resolution;
+  * the ASPP head's GroupNorm (ops.GNConcatFn: onda_gn_fwd / onda_gn_bwd, the same kernels) at its feature size, 4 x 65 x 129:
+    the five-branch concat (5 x 256 channels into one 1280-channel buffer, ReLU) and the bottleneck (256 channels, Dropout2d
+    multiplier), forward and backward;
   * forward + backward of the DeepLabv2-Resnet50-GN model next to the DeepLabv2-Resnet50 (BatchNorm) model.
 
     python tools/gn_timing.py
@@ -82,6 +85,32 @@ compare(f"shortcut site (layer1, {y.numel() * 4 / 1e6:.0f} MB) forward", {"reduc
 compare("shortcut site (layer1) backward", {"reduction + apply": bwd})
 del y, stats, x
 ops.GN_FUSED_STATS = True
+
+
+def head(n, C, relu, drop):
+    """ops.GNConcatFn on n conv outputs of the head's feature size (the input at 1/8: 65 x 129)."""
+    g = torch.Generator().manual_seed(n)
+    Hf, Wf = (H - 1) // 8 + 1, (W - 1) // 8 + 1
+    ys = [torch.randn(B, Hf, Wf, C, generator=g).to(DEV).requires_grad_(True) for _ in range(n)]
+    gammas = [(0.75 + 0.5 * torch.rand(C, generator=g)).to(DEV).requires_grad_(True) for _ in range(n)]
+    betas = [(0.1 * torch.randn(C, generator=g)).to(DEV).requires_grad_(True) for _ in range(n)]
+    chmul = (torch.empty(B, C).bernoulli_(0.9, generator=g) / 0.9).to(DEV) if drop else None
+    dcat = torch.randn(B, Hf, Wf, n * C, generator=g).to(DEV)
+
+    def forward():
+        with torch.no_grad():
+            return event_time(lambda: ops.GNConcatFn.apply(relu, chmul, *ys, *gammas, *betas))
+
+    def backward():
+        cat = ops.GNConcatFn.apply(relu, chmul, *ys, *gammas, *betas)
+        return event_time(lambda: torch.autograd.grad(cat, ys + gammas + betas, dcat))
+    return forward, backward
+
+
+fwd, bwd = head(5, 256, True, False)  # the ASPP concat: five branches side by side in one 1280-channel buffer
+compare(f"head concat (5 x {B} x 65 x 129 x 256) GroupNorm", {"forward": fwd, "backward": bwd})
+fwd, bwd = head(1, 256, False, True)  # the bottleneck: one tensor, the Dropout2d multiplier
+compare(f"head bottleneck ({B} x 65 x 129 x 256, multiplier) GroupNorm", {"forward": fwd, "backward": bwd})
 
 
 def model(name):
