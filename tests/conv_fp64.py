@@ -12,7 +12,10 @@ Comparator, three ways:
       stream-K piece, one tap or the last partial tile row cannot be diluted by the rest of the tensor;
   (c) exact equality wherever the reference is exact by structure (pixels no tap reaches, taps that only see padding,
       padded head columns, prefilled buffer regions the launch must not touch).
+(a) and (b) take another tensor for their denominators (`scale_ref`) where the result is a sum that cancels: the eval-mode
+epilogue that writes limb planes (eval_conv_ref and its bound, at the end, with the schedule helpers both parity files share).
 """
+import ctypes
 import math
 
 import torch
@@ -166,10 +169,12 @@ def _as_rtc(t, kind):
     return t.reshape(-1, 1, t.shape[-1])  # (a view for a dense tensor; a channel slice is copied in its own dtype)
 
 
-def _block_sums(got, ref, kind):
+def _block_sums(got, ref, kind, scale_ref=None):
     """Per block [row blocks, taps, channel blocks]: sum of (got - ref)^2 and of ref^2, in float64, computed over row chunks
-    so that no fp64 copy of a whole tensor is made."""
+    so that no fp64 copy of a whole tensor is made.  scale_ref: a tensor of ref's shape whose squares take the place of ref's
+    in the denominators -- the error scale of a result that is a cancelling sum (eval_conv_ref's `mag`)."""
     g3, r3 = _as_rtc(got, kind), _as_rtc(ref, kind)
+    s3 = _as_rtc(scale_ref, kind) if scale_ref is not None else None
     R, T, C = r3.shape
     nr, nc = -(-R // BLOCK), -(-C // BLOCK)
     num = torch.zeros(nr, T, nc, dtype=torch.float64, device=ref.device)
@@ -186,7 +191,8 @@ def _block_sums(got, ref, kind):
             return t.reshape(t.shape[0] // BLOCK, BLOCK, T, (C + pc) // BLOCK, BLOCK).sum((1, 4))
 
         num[r0 // BLOCK:r0 // BLOCK + (r1 - r0 + pr) // BLOCK] = sums(d)
-        den[r0 // BLOCK:r0 // BLOCK + (r1 - r0 + pr) // BLOCK] = sums(rc)
+        dc = rc if s3 is None else s3[r0:r1].to(device=ref.device, dtype=torch.float64)
+        den[r0 // BLOCK:r0 // BLOCK + (r1 - r0 + pr) // BLOCK] = sums(dc)
     return num, den
 
 
@@ -202,9 +208,10 @@ def _ratio(num, den):
     return torch.where(den > 0, rel, torch.where(num > 0, torch.full_like(rel, float("inf")), torch.zeros_like(rel)))
 
 
-def measure(got, ref, kind="act"):
-    """(tensor rel-L2, worst block rel-L2, (row block, tap, channel block) of the worst block)."""
-    num, den = _block_sums(got, ref, kind)
+def measure(got, ref, kind="act", scale_ref=None):
+    """(tensor rel-L2, worst block rel-L2, (row block, tap, channel block) of the worst block); relative to `scale_ref`
+    instead of `ref` where one is given (_block_sums)."""
+    num, den = _block_sums(got, ref, kind, scale_ref)
     tensor = _ratio(num.sum(), den.sum()).item()  # (the tensor's squared norms are the sums of its blocks')
     blocks = _ratio(num, den)
     flat = int(blocks.reshape(-1).argmax())
@@ -221,12 +228,12 @@ def exact_violations(got, want, mask=None):
     return int(bad.sum())
 
 
-def check(got, ref, mode, what, kind="act", exact=(), bounds=None):
+def check(got, ref, mode, what, kind="act", exact=(), bounds=None, scale_ref=None):
     """Assert (a) and (b) against BOUNDS[mode] (or `bounds`, from chain_bounds) and every (c) in `exact`: pairs (want, mask)
     -- `got` must equal `want` (a tensor or a number) wherever `mask` is True.  Returns (tensor rel-L2, worst block rel-L2)
-    for the report line."""
+    for the report line.  scale_ref: the denominators' tensor where the error scale is not |ref| (_block_sums)."""
     bound_t, bound_b = bounds or BOUNDS[mode]
-    t, b, where = measure(got, ref, kind)
+    t, b, where = measure(got, ref, kind, scale_ref)
     assert t <= bound_t, f"{what}: relative L2 {t:.3e} > {bound_t:.0e} (worst block {where}: {b:.3e})"
     assert b <= bound_b, f"{what}: worst block (row block, tap, channel block) {where} relative L2 {b:.3e} > {bound_b:.0e}"
     for want, mask in exact:
@@ -235,23 +242,93 @@ def check(got, ref, mode, what, kind="act", exact=(), bounds=None):
     return t, b
 
 
-def flagged(got, ref, mode, kind="act", exact=()):
+def flagged(got, ref, mode, kind="act", exact=(), scale_ref=None):
     """True when `check` would fail (the teeth tests)."""
     try:
-        check(got, ref, mode, "probe", kind, exact)
+        check(got, ref, mode, "probe", kind, exact, scale_ref=scale_ref)
     except AssertionError:
         return True
     return False
 
 
 # ------------------------------------------------------------------------------------------- "f16x2" limb split
-def limb_split(t, limb2_scale=2048.0):
+def limb_split(t, limb2_scale=2048.0, amax=None):
     """(hi, lo) with t == hi + lo as the library splits a tensor into two f16 limbs of t * 2^e, e = 15 - exponent of
-    max|t| (ops.limbs.materialize undoes the same split; the second limb is stored times limb2_scale)."""
+    max|t| (ops.limbs.materialize undoes the same split; the second limb is stored times limb2_scale).  amax: the split
+    uses the scale of that bound instead of max|t| -- planes written under an a-priori bound (the eval-mode conv epilogue)."""
     t = t.double()
-    amax = t.abs().max()
+    amax = t.abs().max() if amax is None else torch.as_tensor(amax, dtype=torch.float64)
     e = 15 - int(torch.frexp(amax.float())[1]) if 0 < amax < 3e38 else 0
     xs = t * 2.0 ** e
     hi = xs.half().double()
     lo = ((xs - hi) * limb2_scale).half().double() / limb2_scale
     return hi * 2.0 ** -e, lo * 2.0 ** -e
+
+
+# ------------------------------------------------------------------ the eval-mode epilogue that writes limb planes
+def eval_conv_ref(x, w, scale, shift, res=None, relu=False, stride=1, dil=1, pad=0, conv=None):
+    """(y, mag) in float64 of conv + folded BatchNorm [+ residual] [+ ReLU] (onda_conv2d_fwd_l2_limbs):
+    y = relu?(conv_fwd(x, w) * scale + shift [+ res]) and, per element and before the ReLU,
+    mag = |conv * scale| + |shift| [+ |res|] -- y is a sum that cancels and is then clipped, so no bound relative to |y|
+    holds; the error scale is the size of its terms (check(..., scale_ref=mag)).  x and res are the operands the kernel
+    received (the materialized limb planes), w / scale / shift the fp32 originals.  conv: conv_fwd(x, w, stride, dil, pad)
+    where the caller has it already (several epilogues of one geometry); it is left unchanged."""
+    y = (conv_fwd(x, w, stride, dil, pad) if conv is None else conv) * scale.double()
+    mag = y.abs() + shift.double().abs()
+    y += shift.double()
+    if res is not None:
+        y += res.double()
+        mag += res.double().abs()
+    return (y.clamp_min(0) if relu else y), mag
+
+
+def fold_bounds_ref(w, scale, shift):
+    """ops.fold_bounds from its definition, as two python floats from float64: max_c |scale_c| * sum_k |w_ck|, max_c |shift_c|."""
+    l1 = w.double().abs().sum(dim=(1, 2, 3))
+    return (scale.double().abs() * l1).max().item(), shift.double().abs().max().item()
+
+
+def limb_out_bound_ref(xtrue, kb, res_true=None):
+    """The a-priori bound the limb-writing epilogue scales its planes by (conv_l2.hip limb_out_bound), in float64:
+    (max|x| * kb[0] + kb[1] [+ max|res|]) * 1.0001."""
+    return (float(xtrue) * kb[0] + kb[1] + (float(res_true) if res_true is not None else 0.0)) * 1.0001
+
+
+# ------------------------------------------------------------------------------------------------ schedule edges
+def _G():
+    """Resident workgroups of the conv kernels (what the schedules count rounds in: onda_conv_ws_floats = 3 tiles each)."""
+    from onda_amd._lib import query
+    return query("onda_conv_ws_floats") // (3 * 128 * 128)
+
+
+def _schedule(M, cout, taps, cin):
+    """(kernel id, balanced, tiles mod G, G).  The kernel id, its tile height and whether the schedule is balanced (statistic
+    rows past ceil(M / BM): stream-K pieces) come from the library's queries; the remainder is this test's own arithmetic
+    over the tile shape the library reported -- it checks that a case was BUILT with the remainder its label names, it does
+    not come from the library."""
+    from onda_amd._lib import query
+    rows = ctypes.c_int(0)
+    total = query("onda_conv_l2_tiles_m_split", M, cout, taps, cin, 0, 0, ctypes.byref(rows))
+    kid = query("onda_conv_l2_kernel_id", M, cout, taps, cin)
+    BM, BN = {0: (256, 128), 1: (128, 128), 2: (256, 64), 3: (256, 128)}[kid]
+    assert rows.value == BM
+    tiles = -(-M // BM) * -(-cout // BN)
+    G = _G() // 2 if BM * BN == 256 * 128 else _G()
+    return kid, total > -(-M // BM), tiles % G, G
+
+
+def _edge_geometries():
+    """(label, geometry row, expected kernel id [library], expected balanced [library], remainder the case is built with
+    [construction check, see _schedule] or None), built from G."""
+    R = _G()
+    G0 = R // 2  # 256 x 128 tiles: one workgroup per CU
+    mk = lambda name, H, W, cin, cout, k, dil=1: (name, H, W, cin, cout, k, 1, dil, dil * (k // 2), False, 0, 0, False, False)
+    return [
+        ("256x128, whole rounds (tiles = G)", mk("e.256x128.exact", 64, 4 * G0, 128, 128, 3), 0, False, 0),
+        ("256x128, remainder 1 (tiles = G + 1), stream-K", mk("e.256x128.rem1", 64, 4 * G0 + 4, 128, 128, 3), 0, True, 1),
+        ("128x128 balanced (stream-K)", mk("e.128x128.sk", 50, 256, 256, 128, 3), 1, True, None),
+        ("256x64 balanced (stream-K)", mk("e.256x64.sk", 100, 256, 256, 64, 3), 2, True, None),
+        ("256x128 long K, not balanced (remainder G - 1)", mk("e.256x128.longk", 2 * G0 - 1, 256, 512, 128, 3), 0, False, G0 - 1),
+        ("continuous stream, whole rounds", mk("e.l2x.exact", G0 // 2, 256, 512, 256, 1), 3, False, 0),
+        ("continuous stream, remainder", mk("e.l2x.rem", G0 // 2 + 1, 256, 512, 256, 1), 3, None, 2),
+    ]

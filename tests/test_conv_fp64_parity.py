@@ -6,8 +6,8 @@ Which launches: every geometry of the table, forward (+ statistics), data gradie
 gradient, at the batch the student trains with (8 paired images in "f16x2", 4 in exact fp32), and in "f16x2" also at the
 step's other batch, 4 images -- the M of the teacher / static / dynamic no-grad passes -- at 512x1024 and at bench.py's config
 5, 1024x2048.  The no-grad passes themselves run the eval-mode epilogue that writes limb planes (BatchNorm folded,
-onda_conv2d_fwd_l2_limbs); that epilogue at every shape is a separate piece of work (test_eval_conv_writes_limb_planes covers
-five shapes): here their geometries run through the train-mode entry points, same kernel choice and schedule."""
+onda_conv2d_fwd_l2_limbs); that epilogue is held to fp64 on every kernel path and at every backbone geometry by
+tests/test_eval_conv_fp64_parity.py: here their geometries run through the train-mode entry points, same kernel choice and schedule."""
 import ctypes
 import gc
 import math
@@ -20,6 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv_fp64 as ref  # noqa: E402
+from conv_fp64 import _edge_geometries, _schedule  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -339,45 +340,6 @@ def test_the_table_is_the_step(tmp_path, mode, size):
 
 
 # ------------------------------------------------------------------------------------------------ schedule edges
-def _G():
-    """Resident workgroups of the conv kernels (what the schedules count rounds in: onda_conv_ws_floats = 3 tiles each)."""
-    from onda_amd._lib import query
-    return query("onda_conv_ws_floats") // (3 * 128 * 128)
-
-
-def _schedule(M, cout, taps, cin):
-    """(kernel id, balanced, tiles mod G, G).  The kernel id, its tile height and whether the schedule is balanced (statistic
-    rows past ceil(M / BM): stream-K pieces) come from the library's queries; the remainder is this test's own arithmetic
-    over the tile shape the library reported -- it checks that a case was BUILT with the remainder its label names, it does
-    not come from the library."""
-    from onda_amd._lib import query
-    rows = ctypes.c_int(0)
-    total = query("onda_conv_l2_tiles_m_split", M, cout, taps, cin, 0, 0, ctypes.byref(rows))
-    kid = query("onda_conv_l2_kernel_id", M, cout, taps, cin)
-    BM, BN = {0: (256, 128), 1: (128, 128), 2: (256, 64), 3: (256, 128)}[kid]
-    assert rows.value == BM
-    tiles = -(-M // BM) * -(-cout // BN)
-    G = _G() // 2 if BM * BN == 256 * 128 else _G()
-    return kid, total > -(-M // BM), tiles % G, G
-
-
-def _edge_geometries():
-    """(label, geometry row, expected kernel id [library], expected balanced [library], remainder the case is built with
-    [construction check, see _schedule] or None), built from G."""
-    R = _G()
-    G0 = R // 2  # 256 x 128 tiles: one workgroup per CU
-    mk = lambda name, H, W, cin, cout, k, dil=1: (name, H, W, cin, cout, k, 1, dil, dil * (k // 2), False, 0, 0, False, False)
-    return [
-        ("256x128, whole rounds (tiles = G)", mk("e.256x128.exact", 64, 4 * G0, 128, 128, 3), 0, False, 0),
-        ("256x128, remainder 1 (tiles = G + 1), stream-K", mk("e.256x128.rem1", 64, 4 * G0 + 4, 128, 128, 3), 0, True, 1),
-        ("128x128 balanced (stream-K)", mk("e.128x128.sk", 50, 256, 256, 128, 3), 1, True, None),
-        ("256x64 balanced (stream-K)", mk("e.256x64.sk", 100, 256, 256, 64, 3), 2, True, None),
-        ("256x128 long K, not balanced (remainder G - 1)", mk("e.256x128.longk", 2 * G0 - 1, 256, 512, 128, 3), 0, False, G0 - 1),
-        ("continuous stream, whole rounds", mk("e.l2x.exact", G0 // 2, 256, 512, 256, 1), 3, False, 0),
-        ("continuous stream, remainder", mk("e.l2x.rem", G0 // 2 + 1, 256, 512, 256, 1), 3, None, 2),
-    ]
-
-
 @pytest.mark.parametrize("i", range(7))
 def test_conv_schedule_edges_against_fp64(i):
     """A schedule branch the step does not reach: the library's dispatch queries confirm the kernel and the (un)balanced
