@@ -504,6 +504,11 @@ int onda_sgd_multi(const OndaSgdEntry* table, int n, float momentum, float weigh
 /* k = k*keep + q*blend  (keep=0, blend=1 copies a buffer, prototypes.py:415-416) */
 typedef struct OndaEmaEntry { float* k; const float* q; int64_t n; float keep; float blend; int first_block; } OndaEmaEntry;
 int onda_ema_multi(const OndaEmaEntry* table, int n, int64_t total_blocks, onda_stream_t s);
+/* a[i] <-> b[i] for every entry, bit for bit, as 4-byte words (float32 tensors: n = numel; int64: n = 2 * numel): the two
+ * BatchNorm state sets of adaptation_model.py:39-72 change places in one launch.  One flat launch like onda_ema_multi; the
+ * pointers need 4-byte alignment only; all a- and b-ranges of a table are pairwise disjoint (caller's contract). */
+typedef struct OndaSwapEntry { uint32_t* a; uint32_t* b; int64_t n; int first_block; } OndaSwapEntry;
+int onda_swap_multi(const OndaSwapEntry* table, int n, int64_t total_blocks, onda_stream_t s);
 
 /* ---- model regularisation (prototypes.py:81-91, :334-336; utils/ewc.py:47-54: the EWC penalty with unit Fisher
  * weights that pulls the student towards the frozen static model).

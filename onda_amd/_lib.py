@@ -54,6 +54,10 @@ class OndaEmaEntry(Structure):
     _fields_ = [("k", c_void_p), ("q", c_void_p), ("n", c_int64), ("keep", c_float), ("blend", c_float), ("first_block", c_int)]
 
 
+class OndaSwapEntry(Structure):
+    _fields_ = [("a", c_void_p), ("b", c_void_p), ("n", c_int64), ("first_block", c_int)]
+
+
 # name -> (restype, argtypes); mirrors include/onda_hip.h one to one
 SIGNATURES = {
     "onda_conv_tiles_m": (I, [I]),
@@ -146,6 +150,7 @@ SIGNATURES = {
     "onda_proto_append": (I, [P, P, P, P, P, I, I, P]),
     "onda_sgd_multi": (I, [P, I, F, F, F, L, P]),
     "onda_ema_multi": (I, [P, I, L, P]),
+    "onda_swap_multi": (I, [P, I, L, P]),
     "onda_multi_tensor_block": (I, []),
     "onda_sqdiff_multi_ws": (L, [L]),
     "onda_sqdiff_multi": (I, [P, I, F, L, P, P, P]),

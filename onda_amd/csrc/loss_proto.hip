@@ -897,6 +897,30 @@ __global__ __launch_bounds__(256) void ema_multi_kernel(const OndaEmaEntry* __re
   for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) e.k[i] = e.k[i] * e.keep + e.q[i] * e.blend;
 }
 
+// a[i] <-> b[i] as 4-byte integer words (no float ever touches them: NaN payloads, -0.0 and the halves of an int64 survive).
+// A thread holds both of its words (vectors) before it stores either; the ranges of a table are pairwise disjoint (the caller's
+// contract), so no other thread reads what it writes.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void swap_multi_kernel(const OndaSwapEntry* __restrict__ table, int n_entries) {
+  int64_t i0, i1;
+  const OndaSwapEntry e = mt_block(table, n_entries, i0, i1);
+  if (mt_vector_block(i0, i1, e.a, e.b)) {
+#pragma unroll
+    for (int k = 0; k < MT_BLOCK / 1024; ++k) {
+      const int64_t i = i0 + (k * 256 + threadIdx.x) * 4;
+      const u32x4 va = *reinterpret_cast<const u32x4*>(e.a + i), vb = *reinterpret_cast<const u32x4*>(e.b + i);
+      *reinterpret_cast<u32x4*>(e.a + i) = vb;
+      *reinterpret_cast<u32x4*>(e.b + i) = va;
+    }
+    return;
+  }
+  for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+    const uint32_t wa = e.a[i], wb = e.b[i];
+    e.a[i] = wb;
+    e.b[i] = wa;
+  }
+}
+
 // The entry points with one thread per pixel: the argument checks they share; the grid of 256-thread workgroups, or 0
 int pixel_blocks(const float* logits, const void* out, int64_t N, int K) {
   return logits && out && K >= 1 && K <= KMAX && N >= 1 ? (int)((N + 255) / 256) : 0;
@@ -1061,6 +1085,12 @@ int onda_multi_tensor_block(void) { return MT_BLOCK; }
 int onda_ema_multi(const OndaEmaEntry* table, int n, int64_t max_n, onda_stream_t s) {
   ONDA_REQUIRE(table && n >= 1 && max_n >= 1 && max_n < (1ll << 31));  // max_n: total blocks (flat launch)
   hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)max_n), dim3(256), 0, ONDA_STREAM(s), table, n);
+  return ONDA_LAUNCH_RESULT();
+}
+
+int onda_swap_multi(const OndaSwapEntry* table, int n, int64_t max_n, onda_stream_t s) {
+  ONDA_REQUIRE(table && n >= 1 && max_n >= 1 && max_n < (1ll << 31));  // max_n: total blocks (flat launch)
+  hipLaunchKernelGGL(swap_multi_kernel, dim3((unsigned)max_n), dim3(256), 0, ONDA_STREAM(s), table, n);
   return ONDA_LAUNCH_RESULT();
 }
 

@@ -11,7 +11,8 @@ _MODULES = [
     "framework.domain_adaptation.methods.adaptation_model", "framework.domain_adaptation.methods.prototype_handler",
     "framework.domain_adaptation.methods.prototypes", "framework.domain_adaptation.methods.prototypes_hybrid_switch",
     "framework.domain_adaptation.methods.prototypes_hswitch", "framework.domain_adaptation.methods.prototypes_vswitch",
-    "framework.domain_adaptation.methods.segmentation", "framework.domain_adaptation.methods.advent_da", "framework.dataset", "framework.dataset.buffer_db",
+    "framework.domain_adaptation.methods.segmentation", "framework.domain_adaptation.methods.advent_da",
+    "framework.domain_adaptation.methods.prototype_advent", "framework.dataset", "framework.dataset.buffer_db",
 ]
 
 

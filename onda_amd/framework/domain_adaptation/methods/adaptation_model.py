@@ -37,12 +37,19 @@ def _batchnorms(model):
 
 
 class batchnorm_stats:
-    """A second set of BatchNorm states next to the live one (BN_POLICY "double": source and target statistics are
-    swapped around the source pass).  Same methods as the reference's class (:39-72)."""
+    """A second set of BatchNorm states next to the live one (BN_POLICY "double" and PROTO_ADVENT: source and target
+    statistics are swapped around the source pass).  Same methods as the reference's class (:39-72).
+
+    On a CUDA model ``exchange()`` is ONE launch (``ops.swap_multi``): the live tensors and the kept ones trade contents, all
+    five keys of every BatchNorm, bit for bit; the kept tensors are persistent objects whose contents change.  On a CPU model,
+    or with ``ONDA_BN_SWAP=0`` in the environment (read at every call: the timing tool's control leg), the reference's
+    copies run -- the same bits by another road."""
 
     def __init__(self, model) -> None:
         self.model = model
         self.memory = {}
+        self._bn_plan = None  # (model, its [(name, BatchNorm2d)]): the module walk, made once per model object
+        self._swap_cache = {}  # ops.swap_multi's launch table
         self.save()
 
     def save(self):
@@ -52,7 +59,25 @@ class batchnorm_stats:
         for name, m in _batchnorms(self.model):
             m.load_state_dict(self.memory[name])
 
+    def _swap_pairs(self):
+        """[(live tensor, kept tensor)] of every key of every BatchNorm, or None where the one-launch route does not apply
+        (switched off, nothing kept, a CPU model).  The module walk is made once per model object; the tensors are looked up at
+        every call, so a rebound buffer (``_flat_int_buffers``) or a fresh ``save()`` gives a new launch table."""
+        if os.environ.get("ONDA_BN_SWAP", "1") == "0" or not self.memory:
+            return None
+        plan = self._bn_plan
+        if plan is None or plan[0] is not self.model:
+            plan = self._bn_plan = (self.model, _batchnorms(self.model))
+        pairs = [(getattr(m, key), kept) for name, m in plan[1] for key, kept in self.memory[name].items()]
+        if not pairs or not all(live.is_cuda and kept.is_cuda for live, kept in pairs):
+            return None
+        return pairs
+
     def exchange(self):
+        pairs = self._swap_pairs()
+        if pairs is not None:
+            ops.swap_multi(pairs, self._swap_cache)
+            return
         live = {name: deepcopy(m.state_dict()) for name, m in _batchnorms(self.model)}
         self.load()
         self.memory = live

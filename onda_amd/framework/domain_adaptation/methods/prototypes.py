@@ -426,10 +426,11 @@ class online_proDA(da_model):
         return out
 
     # ---- the target loss, pipelined ----------------------------------------------------------------------------------
-    def _target_losses(self, out, proto_pred, cls_model):
+    def _target_terms(self, out, predictions):
+        """The low-resolution target loss on the fused kernels: (total, {log entries of its terms}) with total = CE * RCE_ALPHA
+        + RCE * RCE_BETA + REGULARIZER_WEIGHT * regulariser + JS_D * JS (reference :300-333); a term whose weight is not
+        positive is logged as 0."""
         spec = self.cfg_spec
-        batch_size, channels, w, h = out.size()
-        predictions = proto_pred["pseudolabels"].reshape(batch_size, w, h)
         w_ce, w_rce, w_reg = _positive(spec.RCE_ALPHA), _positive(spec.RCE_BETA), _positive(spec.REGULARIZER_WEIGHT)
         w_js = _positive(spec.JS_D)
         js_loss = 0
@@ -442,6 +443,13 @@ class online_proDA(da_model):
                 reg_loss = 0
         else:
             total, ce_loss, rce_loss, reg_loss = ops.seg_losses(out, predictions, w_ce, w_rce, w_reg)
+        return total, {"ce_loss": ce_loss if w_ce > 0 else 0, "rce_loss": rce_loss if w_rce > 0 else 0,
+                       "regularization_loss": reg_loss if w_reg > 0 else 0, "JS Divergance loss": js_loss if w_js > 0 else 0}
+
+    def _target_losses(self, out, proto_pred, cls_model):
+        batch_size, channels, w, h = out.size()
+        predictions = proto_pred["pseudolabels"].reshape(batch_size, w, h)
+        total, terms = self._target_terms(out, predictions)
         penalty = 0
         if self.model_regularization is not None:
             # total_loss += ewc_loss(...) (reference :334-336).  The value joins the total detached: its gradient is the
@@ -457,13 +465,13 @@ class online_proDA(da_model):
             total = total + penalty
         flat = proto_pred["pseudolabels"].reshape(-1)
         return {
-            "ce_loss": ce_loss if w_ce > 0 else 0,
+            "ce_loss": terms["ce_loss"],
             "pseudolabel_pixel_num": ((flat >= 0) * (flat != 255)).float().sum(),
             "output & prototype agreement": (flat == cls_model.long()).float().mean(),
-            "rce_loss": rce_loss if w_rce > 0 else 0,
+            "rce_loss": terms["rce_loss"],
             "sym_loss": total,  # the reference aliases total_loss = sym_loss
-            "regularization_loss": reg_loss if w_reg > 0 else 0,
-            "JS Divergance loss": js_loss if w_js > 0 else 0,
+            "regularization_loss": terms["regularization_loss"],
+            "JS Divergance loss": terms["JS Divergance loss"],
             "Total target loss": total,
             "model regularization": penalty,
         }

@@ -1,5 +1,5 @@
 """Multi-tensor launches over device tables (pinned staging buffers): duplicate-replaying SGD (plain and EWC-anchored), teacher
-EMA, the EWC penalty's value."""
+EMA, the EWC penalty's value, the swap of two tensor sets."""
 import ctypes
 import os
 from ctypes import byref
@@ -118,3 +118,48 @@ def ema_multi(items, cache=None):
     call("onda_ema_multi", _p(table), n, first, _stream())
     torch.autograd.graph.increment_version([k for k, *_ in items])
 
+
+def swap_multi(pairs, cache=None):
+    """pairs: list of (a, b): the contents of a and b change places, bit for bit, one launch for all tensors
+    (onda_swap_multi; float32 and int64 alike -- the words move as integers).  `cache` (a dict the caller keeps next to a
+    FIXED list of tensors): the device table is rebuilt only when an address, a size or a dtype changed.  The kernel's contract
+    is checked whenever the table is built: per pair the same dtype, numel and device, contiguous, element size 4 or 8, and
+    no address range twice in the table."""
+    if not pairs:
+        return
+    # (size and dtype belong to the key: a tensor reallocated at a kept address goes through the checks again)
+    key = [(a.data_ptr(), b.data_ptr(), a.numel(), b.numel(), a.dtype, b.dtype) for a, b in pairs]
+    if cache is not None and cache.get("key") == key:
+        table, n, first = cache["table"], cache["n"], cache["blocks"]
+    else:
+        found, spans = [], []
+        dev = pairs[0][0].device
+        for a, b in pairs:
+            if a.dtype != b.dtype or a.numel() != b.numel():
+                raise ValueError(f"swap_multi: a pair of {a.dtype}[{a.numel()}] and {b.dtype}[{b.numel()}]")
+            if a.element_size() not in (4, 8) or not (a.is_contiguous() and b.is_contiguous()):
+                raise ValueError("swap_multi: contiguous tensors of 4- or 8-byte elements only")
+            if a.device != dev or b.device != dev:
+                raise ValueError("swap_multi: every tensor of a table on one device")
+            words = a.numel() * a.element_size() // 4
+            if words == 0:
+                continue
+            spans += [(a.data_ptr(), a.data_ptr() + 4 * words), (b.data_ptr(), b.data_ptr() + 4 * words)]
+            found.append((a.data_ptr(), b.data_ptr(), words))
+        spans.sort()
+        for (_, end), (start, _) in zip(spans, spans[1:]):
+            if start < end:
+                raise ValueError("swap_multi: an address range appears twice in the table")
+        if dev.type != "cuda":
+            raise ValueError("swap_multi: device tensors only (the library has no CPU path)")
+        blk, ents, first = query("onda_multi_tensor_block"), [], 0
+        for pa, pb, words in found:
+            ents.append(_lib.OndaSwapEntry(pa, pb, words, first))
+            first += -(-words // blk)
+        table, n = (_table(ents, _lib.OndaSwapEntry, dev), len(ents)) if ents else (None, 0)
+        if cache is not None:
+            cache.update(key=key, table=table, n=n, blocks=first)
+    if n:
+        call("onda_swap_multi", _p(table), n, first, _stream())
+    # HipBatchNorm2d.folded() and the bound caches key on _version
+    torch.autograd.graph.increment_version([t for pair in pairs for t in pair])
