@@ -43,12 +43,22 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+__device__ __forceinline__ f32x4 splat4(float x) { return f32x4{x, x, x, x}; }
+__device__ __forceinline__ f32x4 relu4(f32x4 v) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.f);
+  return v;
+}
+// Running max|v| of a pass over four values a step (folded into the tensor's slots at the end of the kernel, below).
+__device__ __forceinline__ float max_abs4(float mx, const f32x4 v) {
+  return fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+}
 
 // Running max|x| of a tensor for the "f16x2" convolutions.  The value lives in ONDA_AMAX_FLOATS device floats
 // (all zero before the producer runs), used as ONDA_AMAX_SLOTS slots one 128-byte line apart: L2 serialises
 // atomics per line, so the slots are what lets thousands of workgroups fold their maxima without queueing.
 // A producer does one atomicMax on the bit pattern (monotonic for non-negative floats) per workgroup
-// (amax_update_block) or per wave (amax_update); a consumer takes the maximum over the slots (amax_read).
+// (tile_amax_publish) or per wave (amax_update); a consumer takes the maximum over the slots (amax_read).
 // max is order-independent: the result is deterministic.  Every lane / thread must call these.
 constexpr int AMAX_STRIDE = ONDA_AMAX_FLOATS / ONDA_AMAX_SLOTS;
 __device__ __forceinline__ void amax_update(float* amax, float m) {
@@ -57,13 +67,21 @@ __device__ __forceinline__ void amax_update(float* amax, float m) {
     atomicMax(reinterpret_cast<unsigned*>(amax) + ((blockIdx.x * 4 + (threadIdx.x >> 6)) & (ONDA_AMAX_SLOTS - 1)) * AMAX_STRIDE,
               __float_as_uint(m));
 }
-// one atomic per 256-thread workgroup; `red`: 4 floats of LDS
-__device__ __forceinline__ void amax_update_block(float* amax, float m, float* red) {
+// max of N floats as a balanced tree: for N = 4 the expression fmaxf(fmaxf(v0, v1), fmaxf(v2, v3)) the 256-thread kernels have
+// always had (a left-to-right loop gives them other code), the same shape for 8
+template <int N>
+__device__ __forceinline__ float max_of(const float* v) {
+  if constexpr (N == 1) return v[0];
+  else return fmaxf(max_of<N / 2>(v), max_of<N - N / 2>(v + N / 2));
+}
+// one atomic per workgroup of NW waves (4: the 256-thread kernels); `red`: NW floats of LDS
+template <int NW = 4>
+__device__ __forceinline__ void tile_amax_publish(float* amax, float m, float* red) {
   m = wave_max(m);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    m = max_of<NW>(red);
     if (m > 0.f)
       atomicMax(reinterpret_cast<unsigned*>(amax) + (blockIdx.x & (ONDA_AMAX_SLOTS - 1)) * AMAX_STRIDE, __float_as_uint(m));
   }

@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void conv_fixup_kernel(const ConvK a, int G, c
   f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
   if (vn && a.scale) sc = *reinterpret_cast<const f32x4*>(a.scale + n);
   if (vn && a.shift) sh = *reinterpret_cast<const f32x4*>(a.shift + n);
-  const bool plain = (c.out_os == 1 && c.Hf == c.Ho && c.Wf == c.Wo);
+  const bool plain = dense_out(c);
 
   // contributing workgroups (ascending = the fixed summation order) and the slot each used
   __shared__ int piece[1024];
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void conv_fixup_kernel(const ConvK a, int G, c
   __syncthreads();
 
   f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 vmin = {3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f}, vmax = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+  f32x4 vmin = splat4(STAT_MIN_ID), vmax = splat4(STAT_MAX_ID);
   float mx = 0.f;
 #pragma unroll 2
   for (int i = 0; i < RPT; ++i) {
@@ -260,23 +260,12 @@ __global__ __launch_bounds__(256) void conv_fixup_kernel(const ConvK a, int G, c
     }
     const int m = m0 + row;
     if (m >= a.M || !vn) continue;
-    f32x4 o = v * sc + sh;
-    if (a.res) o += *reinterpret_cast<const f32x4*>(a.res + (size_t)m * c.ldr + n);
-    if (c.relu) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = fmaxf(o[j], 0.f);
-    }
-    size_t orow = m;
-    if (!plain) {
-      const int wo = m % c.Wo, tq = m / c.Wo;
-      const int ho = tq % c.Ho, b = tq / c.Ho;
-      orow = ((size_t)b * c.Hf + (size_t)ho * c.out_os) * c.Wf + (size_t)wo * c.out_os;
-    }
-    *reinterpret_cast<f32x4*>(a.y + orow * c.ldy + n) = o;
-    mx = fmaxf(fmaxf(mx, fmaxf(fabsf(o[0]), fabsf(o[1]))), fmaxf(fabsf(o[2]), fabsf(o[3])));
+    const f32x4 o = conv_out4(v, sc, sh, a.res ? reinterpret_cast<const f32x4*>(a.res + (size_t)m * c.ldr + n) : nullptr, c.relu);
+    *reinterpret_cast<f32x4*>(a.y + (plain ? (size_t)m : out_row(c, m)) * c.ldy + n) = o;
+    mx = max_abs4(mx, o);
   }
   __shared__ float amax_red[4];
-  if (a.amax != nullptr) amax_update_block(a.amax, mx, amax_red);
+  if (a.amax != nullptr) tile_amax_publish(a.amax, mx, amax_red);
   if (a.stats != nullptr) {
     const int SR = a.stats_rows;
     red[0][t] = s1;

@@ -160,7 +160,43 @@ __device__ __forceinline__ void conv_store_partial(float* slot, const typename A
       }
 }
 
-// `red`: >= WAVES_M*BN*2 + 2*WAVES_M floats of LDS that no wave is still reading.
+// ---- what every convolution does to a finished tile, piece by piece (the tile epilogues and the stream-K fix-ups of conv.hip
+// and conv_l2.hip) ----
+// row m of the GEMM is row m of y: every convolution but the strided data gradient
+__device__ __forceinline__ bool dense_out(const OndaConv& c) { return c.out_os == 1 && c.Hf == c.Ho && c.Wf == c.Wo; }
+// ... whose GEMM row m (an output pixel of the strided conv) goes to this row of y (the pixel it sampled)
+__device__ __forceinline__ size_t out_row(const OndaConv& c, int m) {
+  const int wo = m % c.Wo, tq = m / c.Wo;
+  const int ho = tq % c.Ho, b = tq / c.Ho;
+  return ((size_t)b * c.Hf + (size_t)ho * c.out_os) * c.Wf + (size_t)wo * c.out_os;
+}
+// the per-channel minimum and maximum of no rows at all (statistic rows 2 and 3; rows 0 and 1, the sums, start at 0)
+constexpr float STAT_MIN_ID = 3.0e38f, STAT_MAX_ID = -3.0e38f;
+// v * sc + sh.  FUSED: rounded once (the expression is contracted to an fma), what the tile epilogues and conv_fixup_kernel
+// compute; not FUSED: the product is rounded before the shift is added -- conv_l2_fixup_kernel, which applied its scale and its
+// shift under separate tests, keeps its bits that way
+template <bool FUSED>
+__device__ __forceinline__ f32x4 affine4(f32x4 v, f32x4 sc, f32x4 sh) {
+  if constexpr (FUSED) {
+    return v * sc + sh;
+  } else {
+#pragma clang fp contract(off)
+    const f32x4 p = v * sc;
+    return p + sh;
+  }
+}
+// fp32 output of four columns: v in the operands' own units, sc / sh the columns' scale and shift (1 and 0: none), res: the
+// residual's four values (null: none)
+template <bool FUSED = true>
+__device__ __forceinline__ f32x4 conv_out4(f32x4 v, f32x4 sc, f32x4 sh, const f32x4* res, bool relu) {
+  v = affine4<FUSED>(v, sc, sh);
+  if (res != nullptr) v += *res;
+  if (relu) v = relu4(v);
+  return v;
+}
+
+// `red`: >= WAVES_M*BN*2 + 2*WAVES_M floats of LDS that no wave is still reading.  (A lane of the 32 x 32 accumulator layout
+// holds ONE column per MFMA tile, so the output expression stands here in scalar form, not as conv_out4.)
 template <int BM, int BN, int TM, int TN, int WAVES_M, int MF = 32>
 __device__ __forceinline__ void conv_epilogue(const ConvK& a, const typename AccTile<MF>::T (&acc)[TM][TN],
                                               float* red, int tile_m, int m0, int n0, int wm, int wn, int lane) {
@@ -203,7 +239,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& a, const typename Acc
     }
   }
 
-  const bool plain = (c.out_os == 1 && c.Hf == c.Ho && c.Wf == c.Wo);
+  const bool plain = dense_out(c);
   float mx = 0.f;
 #pragma unroll
   for (int jn = 0; jn < TN; ++jn) {
@@ -220,30 +256,13 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& a, const typename Acc
         float v = acc[i][jn][e] * sc + sh;
         if (a.res) v += a.res[(size_t)m * c.ldr + n];
         if (c.relu) v = fmaxf(v, 0.f);
-        size_t orow = m;
-        if (!plain) {
-          const int wo = m % c.Wo, tq = m / c.Wo;
-          const int ho = tq % c.Ho, b = tq / c.Ho;
-          orow = ((size_t)b * c.Hf + (size_t)ho * c.out_os) * c.Wf + (size_t)wo * c.out_os;
-        }
-        a.y[orow * c.ldy + n] = v;
+        a.y[(plain ? (size_t)m : out_row(c, m)) * c.ldy + n] = v;
         mx = fmaxf(mx, fabsf(v));
       }
     }
   }
-  if (a.amax != nullptr) {  // one atomic per tile: max over the workgroup's waves through LDS (past the statistics' scratch)
-    float* ar = red + WAVES_M * BN * 2;
-    mx = wave_max(mx);
-    if ((t & 63) == 0) ar[t >> 6] = mx;
-    __syncthreads();
-    if (t == 0) {
-      float m = ar[0];
-#pragma unroll
-      for (int w_ = 1; w_ < 2 * WAVES_M; ++w_) m = fmaxf(m, ar[w_]);
-      if (m > 0.f)
-        atomicMax(reinterpret_cast<unsigned*>(a.amax) + (blockIdx.x & (ONDA_AMAX_SLOTS - 1)) * AMAX_STRIDE, __float_as_uint(m));
-    }
-  }
+  // one atomic per tile: max over the workgroup's waves through LDS (past the statistics' scratch)
+  if (a.amax != nullptr) tile_amax_publish<2 * WAVES_M>(a.amax, mx, red + WAVES_M * BN * 2);
 }
 
 // conv.hip: sums stream-K partial tiles and runs the epilogue for split tiles

@@ -23,7 +23,7 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
   // a flat tensor (rows == 1) whose length is not a multiple of 4: the last 1-3 values
   if (rows == 1 && blockIdx.x == 0 && threadIdx.x < (C & 3)) m = fmaxf(m, fabsf(x[(C & ~3) + threadIdx.x]));
   __shared__ float red[4];
-  amax_update_block(amax, m, red);
+  tile_amax_publish(amax, m, red);
 }
 
 // OIHW fp32 -> limb rows dst[rows_pad][Kp / 32][2][32] f16 of w * 2^e (e from *amax; limbs.h).  dgrad = 0: row n,
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void absmax_multi_kernel(const OndaPackEntry* 
   float m = 0.f;
   for (long long i = i0 + threadIdx.x; i < i1; i += 256) m = fmaxf(m, fabsf(e.w[i]));
   __shared__ float red[4];
-  amax_update_block(e.amax, m, red);
+  tile_amax_publish(e.amax, m, red);
 }
 
 // Both packed forms of a weight in one pass over it, through LDS: a workgroup takes 32 output x 32 input channels x all

@@ -196,15 +196,7 @@ __global__ __launch_bounds__(256) void stem_im2col_l2_kernel(const float* __rest
   }
 }
 
-// ---- epilogue of a (64*WM) x (64*WN) tile held as 4 x 4 MFMA tiles of 16 x 16 per wave ----------------------------
-// The accumulator layout has a lane's 16 values of one MFMA column 4 rows apart: stored as they stand that is 64
-// four-byte stores per lane in 64-byte runs, and the store ISSUE (not bandwidth) is what a tile then waits for
-// (measured: 26 000 cycles per 256 x 128 tile, more than the K loop of a 1 x 1 convolution with 256 input
-// channels).  So each wave transposes its 64 x 64 sub-tile through LDS, 16 rows at a time, and stores whole
-// 256-byte row segments as 16-byte vectors: 16 stores per lane, scale / shift loaded once per lane.
-// `scratch`: LDS nobody else touches during the epilogue: 4 KiB per wave, then WM*BN*4 + WM*WN floats of statistics.
-// COUNTED: every wave issues exactly 16 output stores (buffer stores; rows past M / channels past Cout get an
-// out-of-range offset and are dropped by the hardware) -- conv_l2x_kernel counts them in its vmcnt waits.
+// ---- pieces of the output side that the tile epilogues, conv_l2a_kernel and conv_l2_fixup_kernel share -------------------------
 // x[lane] (+, min, max) x[lane ^ 16] and x[lane ^ 32] on the VALU (v_permlane16/32_swap: gfx950), four values per call.
 // (Inline assembly: this compiler folds the builtin's two results into one when both inputs are the same value.)
 #define ONDA_SWAP4(INSN, A, B)                                                                                          \
@@ -224,6 +216,96 @@ __device__ __forceinline__ void rows_reduce4(float& s1, float& s2, float& mn, fl
 #endif
 }
 
+constexpr int TRS = 68;  // floats per row of a wave's transposition buffer (16 rows): rows 4 apart land 16 banks apart (ds_write_b32
+                         // banks are (a/4) % 32 per 32-lane half; 64 would put lanes l and l+16 on one bank)
+// row block i of a wave's grid of 16 x 16 tiles -> its transposition buffer; lane l then holds row 4*r + (l >> 4) of the 16-row
+// chunk (r = 0..3), columns 4*(l & 15) .. +3.  One wave, and the LDS executes a wave's instructions in order: no wait, no s_barrier.
+// (A macro, like MFMA_SNAKE: as a function it cost every tile kernel 8 to 20 bytes of scratch; docs/experiments.md.)
+#define TRANSPOSE_WRITE(TR, ROW, LANE)                                                                                  \
+  do {                                                                                                                  \
+    _Pragma("unroll") for (int jn = 0; jn < 4; ++jn) _Pragma("unroll") for (int e = 0; e < 4; ++e)                      \
+        (TR)[(4 * ((LANE) >> 4) + e) * TRS + jn * 16 + ((LANE) & 15)] = (ROW)[jn][e];                                    \
+    __builtin_amdgcn_wave_barrier();                                                                                    \
+  } while (0)
+// statistics of column block JN over a wave's 16 * MI rows, before the reduction over the lanes that hold its other rows: sum, sum
+// of squares, min, max of the RAW sums; declares S1 .. MXV (a macro for the same reason: as a function, 4 bytes in two kernels)
+#define COL_STATS(ACC, MI, JN, S1, S2, MN, MXV)                                                                         \
+  float S1 = 0.f, S2 = 0.f, MN = STAT_MIN_ID, MXV = STAT_MAX_ID;                                                        \
+  _Pragma("unroll") for (int i = 0; i < (MI); ++i) _Pragma("unroll") for (int e = 0; e < 4; ++e) {                      \
+    const float v = ACC[i][JN][e];                                                                                      \
+    S1 += v;                                                                                                            \
+    S2 += v * v;                                                                                                        \
+    MN = fminf(MN, v);                                                                                                  \
+    MXV = fmaxf(MXV, v);                                                                                                \
+  }
+// the tile's statistic rows: the WM row groups of `red` summed in ascending order -> stats[tile_m][SR][Cout]
+template <int WM, int WN>
+__device__ __forceinline__ void tile_stats_store(const ConvK& a, const float* red, int tile_m, int n0) {
+  constexpr int BN = 64 * WN, NT = WM * WN * 64;
+  const OndaConv& c = a.c;
+  const int SR = a.stats_rows;  // 2, or 4: + min / max of the raw tile (rows past M count as zeros: they only have to BOUND, norm_l2.hip)
+  for (int col = threadIdx.x; col < BN; col += NT) {
+    if (n0 + col >= c.Cout) continue;
+    float s1 = 0.f, s2 = 0.f, mn = STAT_MIN_ID, mxv = STAT_MAX_ID;
+#pragma unroll
+    for (int w_ = 0; w_ < WM; ++w_) {
+      s1 += red[(w_ * BN + col) * 4 + 0];
+      s2 += red[(w_ * BN + col) * 4 + 1];
+      mn = fminf(mn, red[(w_ * BN + col) * 4 + 2]);
+      mxv = fmaxf(mxv, red[(w_ * BN + col) * 4 + 3]);
+    }
+    float* dst = a.stats + (size_t)tile_m * SR * c.Cout + n0 + col;
+    dst[0] = s1;
+    dst[c.Cout] = s2;
+    if (SR == 4) {
+      dst[2 * c.Cout] = mn;
+      dst[3 * c.Cout] = mxv;
+    }
+  }
+}
+
+// ---- LIMB-PLANE output (eval mode: conv + folded BatchNorm [+ residual limbs] [+ ReLU] -> the next conv's operand format, no
+// fp32 tensor and no split pass in between).  The planes' scale has to exist before the first element is stored: it comes
+// from an a-priori bound
+//     max|y| <= max|x| * max_c(|scale_c| * sum_k |w_ck|) + max_c |shift_c| + max|residual|
+// (every workgroup computes it from three device scalars and writes it to its slot of `ybound`: same value everywhere).
+// The bound is 2^7..2^10 above the true maximum for these layers; a scale 2^k too small costs k of the 28 bits of range
+// the format has below the maximum, nothing else.  The TRUE maximum of the stored values still goes to `amax` (one atomic
+// per tile), because it is what bounds the NEXT layer: bounds do not compound.
+__device__ __forceinline__ float limb_out_bound(const ConvK& a) {
+  float b = amax_read(a.xtrue) * a.kb[0] + a.kb[1];
+  if (a.resl != nullptr) b += amax_read(a.res_true);
+  return b * 1.0001f;  // (fp32 rounding of the sums and of the bound itself)
+}
+// what a workgroup (thread t of it) settles before its first limb store: the planes' scale `so`, the residual planes' unscale `ri`
+struct LimbOutScale { float so, ri; };
+__device__ __forceinline__ LimbOutScale limb_out_scale(const ConvK& a, int t) {
+  const float bound = limb_out_bound(a);
+  const float so = scale_from(bound).s;
+  if (t == 0) a.ybound[(blockIdx.x & (ONDA_AMAX_SLOTS - 1)) * AMAX_STRIDE] = bound;
+  return {so, a.resl != nullptr ? scale_of(a.res_amax).inv : 0.f};
+}
+// limb output of four columns: the value (what the true maximum is taken of) and its two limbs under the planes' scale; v, sc, sh,
+// FUSED as for conv_out4; r1 / r2: the residual's limbs, read where has_res (by value: by reference they went to the stack)
+template <bool FUSED = true>
+__device__ __forceinline__ f32x4 limb_out4(LimbOutScale h, f32x4 v, f32x4 sc, f32x4 sh, bool has_res, u32x2 r1, u32x2 r2, bool relu,
+                                           u32x2& l1, u32x2& l2) {
+  v = affine4<FUSED>(v, sc, sh);
+  if (has_res) v += join4(r1, r2) * h.ri;
+  if (relu) v = relu4(v);
+  split4(v * h.so, l1, l2);
+  return v;
+}
+
+// ---- epilogue of a (64*WM) x (64*WN) tile held as 4 x 4 MFMA tiles of 16 x 16 per wave ----------------------------
+// The accumulator layout has a lane's 16 values of one MFMA column 4 rows apart: stored as they stand that is 64
+// four-byte stores per lane in 64-byte runs, and the store ISSUE (not bandwidth) is what a tile then waits for
+// (measured: 26 000 cycles per 256 x 128 tile, more than the K loop of a 1 x 1 convolution with 256 input
+// channels).  So each wave transposes its 64 x 64 sub-tile through LDS, 16 rows at a time, and stores whole
+// 256-byte row segments as 16-byte vectors: 16 stores per lane, scale / shift loaded once per lane.
+// `scratch`: LDS nobody else touches during the epilogue: 4 KiB per wave, then WM*BN*4 + WM*WN floats of statistics.
+// COUNTED: every wave issues exactly 16 output stores (buffer stores; rows past M / channels past Cout get an
+// out-of-range offset and are dropped by the hardware) -- conv_l2x_kernel counts them in its vmcnt waits.
 // AFFINE = false: no per-channel scale / shift, residual or ReLU (train-mode convolutions, plain data gradients): the
 // epilogue then issues no global LOAD at all.  That matters in the continuous stream (COUNTED): vmcnt counts in issue
 // order, so waiting for any load issued here means waiting for the next tile's DMAs that are already in flight, and
@@ -235,31 +317,17 @@ __device__ __forceinline__ void l2_epilogue(const ConvK& a, const f32x4 (&acc)[4
                                             int n0, int wm, int wn, int lane, float ua, float ub, unsigned y_bytes = 0) {
   // `acc` holds RAW sums (operand units: value * 2^ea * 2^eb); ua = 2^-ea, ub = 2^-eb (exact) are applied to the four
   // statistics of a column and folded into the per-channel scale of the output instead of to all 64 accumulators
-  constexpr int BN = 64 * WN, NW = WM * WN, NT = NW * 64;
-  constexpr int TRS = 68;  // floats per row of the transposition buffer: rows 4 apart land 16 banks apart (ds_write_b32
-                           // banks are (a/4) % 32 per 32-lane half; 64 would put lanes l and l+16 on one bank)
+  constexpr int BN = 64 * WN, NW = WM * WN;
   const OndaConv& c = a.c;
   const int t = threadIdx.x, wave = t >> 6;
   // diagnostics: the phases of the workgroup's LAST tile (overwritten per tile: no load here, see AFFINE)
   unsigned long long* est = a.stamps != nullptr && t == 0 ? a.stamps + (size_t)blockIdx.x * 32 + 24 : nullptr;
   if (est) est[0] = __builtin_amdgcn_s_memtime();
   float* red = reinterpret_cast<float*>(scratch + NW * (16 * TRS * 4));
-  const int SR = a.stats_rows;  // 2, or 4 with the per-channel min / max of the raw tile (rows past M count as zeros:
-                                // the extrema only have to BOUND the tensor's, norm_l2.hip)
   if (a.stats != nullptr) {
 #pragma unroll
     for (int jn = 0; jn < 4; ++jn) {
-      float s1 = 0.f, s2 = 0.f, mn = 3.0e38f, mxv = -3.0e38f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float v = acc[i][jn][e];
-          s1 += v;
-          s2 += v * v;
-          mn = fminf(mn, v);
-          mxv = fmaxf(mxv, v);
-        }
+      COL_STATS(acc, 4, jn, s1, s2, mn, mxv);
       rows_reduce4(s1, s2, mn, mxv);
       if (lane < 16) {
         const int col = (wn * 4 + jn) * 16 + lane;
@@ -272,7 +340,7 @@ __device__ __forceinline__ void l2_epilogue(const ConvK& a, const f32x4 (&acc)[4
   }
 
   if (est) est[1] = __builtin_amdgcn_s_memtime();
-  const bool plain = (c.out_os == 1 && c.Hf == c.Ho && c.Wf == c.Wo);
+  const bool plain = dense_out(c);
   // after the transposition: lane -> row 4*r + (lane >> 4) of a 16-row chunk (r = 0..3), columns 4*(lane & 15) .. +3
   const int cl = (lane & 15) * 4, rl = lane >> 4;
   const int n = n0 + wn * 64 + cl;
@@ -316,11 +384,7 @@ __device__ __forceinline__ void l2_epilogue(const ConvK& a, const f32x4 (&acc)[4
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     // this wave's own rows of the buffer: only its own earlier reads have to be out of the way
-#pragma unroll
-    for (int jn = 0; jn < 4; ++jn)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) tr[(4 * (lane >> 4) + e) * TRS + jn * 16 + (lane & 15)] = acc[i][jn][e];
-    __builtin_amdgcn_wave_barrier();  // one wave, and the LDS executes a wave's instructions in order: no wait, no s_barrier
+    TRANSPOSE_WRITE(tr, acc[i], lane);  // one wave, and the LDS executes a wave's instructions in order: no wait, no s_barrier
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = 4 * r + rl;
@@ -328,12 +392,11 @@ __device__ __forceinline__ void l2_epilogue(const ConvK& a, const f32x4 (&acc)[4
       const int m = mw + i * 16 + 4 * r;
       const bool live = (full_rows || m < a.M) && vn;
       if constexpr (AFFINE) {
+        // conv_out4, written out (and out_row below): through the functions the tile kernels' code changed and the evaluation
+        // pass measured outside the parent's range (docs/experiments.md)
         v = v * sc + sh;
         if (a.res) v += rv[i][r];
-        if (c.relu) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.f);
-        }
+        if (c.relu) v = relu4(v);
       } else {
         v = v * sc;
       }
@@ -360,7 +423,7 @@ __device__ __forceinline__ void l2_epilogue(const ConvK& a, const f32x4 (&acc)[4
           store_out(reinterpret_cast<f32x4*>(a.y + orow * c.ldy + n), v);
         }
       }
-      if (track && live) mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+      if (track && live) mx = max_abs4(mx, v);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -379,26 +442,7 @@ __device__ __forceinline__ void l2_epilogue(const ConvK& a, const f32x4 (&acc)[4
     }
   }
   if (est) est[3] = __builtin_amdgcn_s_memtime();
-  if (a.stats != nullptr) {
-    for (int col = t; col < BN; col += NT) {
-      if (n0 + col >= c.Cout) continue;
-      float s1 = 0.f, s2 = 0.f, mn = 3.0e38f, mxv = -3.0e38f;
-#pragma unroll
-      for (int w_ = 0; w_ < WM; ++w_) {
-        s1 += red[(w_ * BN + col) * 4 + 0];
-        s2 += red[(w_ * BN + col) * 4 + 1];
-        mn = fminf(mn, red[(w_ * BN + col) * 4 + 2]);
-        mxv = fmaxf(mxv, red[(w_ * BN + col) * 4 + 3]);
-      }
-      float* dst = a.stats + (size_t)tile_m * SR * c.Cout + n0 + col;
-      dst[0] = s1;
-      dst[c.Cout] = s2;
-      if (SR == 4) {
-        dst[2 * c.Cout] = mn;
-        dst[3 * c.Cout] = mxv;
-      }
-    }
-  }
+  if (a.stats != nullptr) tile_stats_store<WM, WN>(a, red, tile_m, n0);
   if (a.amax != nullptr && t == 0) {  // one atomic per tile
     float m = ar[0];
 #pragma unroll
@@ -409,34 +453,17 @@ __device__ __forceinline__ void l2_epilogue(const ConvK& a, const f32x4 (&acc)[4
   if (est) est[4] = __builtin_amdgcn_s_memtime();
 }
 
-// ---- epilogue that writes LIMB PLANES (eval mode: conv + folded BatchNorm [+ residual limbs] [+ ReLU] -> the next conv's
-// operand format, no fp32 tensor and no split pass in between).  The planes' scale has to exist before the first element
-// is stored: it comes from an a-priori bound
-//     max|y| <= max|x| * max_c(|scale_c| * sum_k |w_ck|) + max_c |shift_c| + max|residual|
-// (every workgroup computes it from three device scalars and writes it to its slot of `ybound`: same value everywhere).
-// The bound is 2^7..2^10 above the true maximum for these layers; a scale 2^k too small costs k of the 28 bits of range
-// the format has below the maximum, nothing else.  The TRUE maximum of the stored values still goes to `amax` (one atomic
-// per tile), because it is what bounds the NEXT layer: bounds do not compound.
-__device__ __forceinline__ float limb_out_bound(const ConvK& a) {
-  float b = amax_read(a.xtrue) * a.kb[0] + a.kb[1];
-  if (a.resl != nullptr) b += amax_read(a.res_true);
-  return b * 1.0001f;  // (fp32 rounding of the sums and of the bound itself)
-}
-
 template <int WM, int WN, bool COUNTED>
 __device__ __forceinline__ void l2_epilogue_limbs(const ConvK& a, const f32x4 (&acc)[4][4], unsigned char* scratch, int m0, int n0,
                                                   int wm, int wn, int lane, float ua, float ub) {
   constexpr int BN = 64 * WN, NW = WM * WN;
-  constexpr int TRS = 68;
   const OndaConv& c = a.c;
   if constexpr (COUNTED) asm volatile("" : "+v"(lane));
   int t = threadIdx.x;
   if constexpr (COUNTED) asm volatile("" : "+v"(t));
   const int wave = t >> 6;
-  const float bound = limb_out_bound(a);
-  const float so = scale_from(bound).s;
-  if (t == 0) a.ybound[(blockIdx.x & (ONDA_AMAX_SLOTS - 1)) * AMAX_STRIDE] = bound;
-  const float ri = a.resl != nullptr ? scale_of(a.res_amax).inv : 0.f;
+  const LimbOutScale lo = limb_out_scale(a, t);
+  const float so = lo.so, ri = lo.ri;
   const int cl = (lane & 15) * 4, rl = lane >> 4;
   const int n = n0 + wn * 64 + cl;
   const bool vn = n < c.Cout;
@@ -468,28 +495,21 @@ __device__ __forceinline__ void l2_epilogue_limbs(const ConvK& a, const f32x4 (&
   _Float16* const ytile = a.yl + (size_t)m0 * 2 * c.ldy;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int jn = 0; jn < 4; ++jn)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) tr[(4 * (lane >> 4) + e) * TRS + jn * 16 + (lane & 15)] = acc[i][jn][e];
-    __builtin_amdgcn_wave_barrier();
+    TRANSPOSE_WRITE(tr, acc[i], lane);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = 4 * r + rl;
       f32x4 v = *reinterpret_cast<const f32x4*>(tr + row * TRS + cl);
       const int m = mw + i * 16 + 4 * r;
       const bool live = m < a.M && vn;
-      v = v * sc + sh;
+      v = v * sc + sh;  // (limb_out4, written out: see l2_epilogue)
       if (a.resl != nullptr) {
         const f32x4 j = join4(r1[i][r], r2[i][r]);
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] += j[q] * ri;
       }
-      if (c.relu) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.f);
-      }
-      if (live) mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+      if (c.relu) v = relu4(v);
+      if (live) mx = max_abs4(mx, v);
       u32x2 l1, l2;
       split4(v * so, l1, l2);
       if constexpr (COUNTED) {
@@ -1075,7 +1095,6 @@ __global__ __launch_bounds__(512, 2) void conv_l2a_kernel(const ConvK a, unsigne
   constexpr int NWAIT = (AHEAD - 1) * BPW + (ONDA_L2A_PADS ? AHEAD * EPS : 0);  // operations younger than the DMAs a K-step waits for
   static_assert(NWAIT <= 63, "vmcnt holds 6 bits");
   static_assert((KB == 8 || KB == 4 || KB == 2) && EPI == 0, "schedules of ep_step");
-  constexpr int TRS = 68;                  // floats per row of a wave's transposition buffer (l2_epilogue)
   constexpr int SCRATCH = NW * (16 * TRS * 4) + WM * BN * 4 * 4 + 64;  // transposition buffers, statistics partials
   constexpr int A2_BYTES = A2L ? KB * (BM / 16) * 1024 : 0;           // second limbs: [kb][16-row block][16 rows x 64 B]
   constexpr int NA = A2L ? 1 : 2;                                     // limbs of the rows held in registers
@@ -1171,19 +1190,9 @@ __global__ __launch_bounds__(512, 2) void conv_l2a_kernel(const ConvK a, unsigne
   float* const red = reinterpret_cast<float*>(scratch + NW * (16 * TRS * 4));
   const int SR = a.stats_rows;
   auto ep_n = [&]() { return o_n0 + wn * 64 + cl; };
-  // statistics of column block jn: sum, sum of squares, min, max over this wave's 64 rows -> red (l2_epilogue's arithmetic)
+  // statistics of column block jn over this wave's rows -> red
   auto ep_S = [&](int jn) {
-    float s1 = 0.f, s2 = 0.f, mn = 3.0e38f, mxv = -3.0e38f;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float v = old[i][jn][e];
-        s1 += v;
-        s2 += v * v;
-        mn = fminf(mn, v);
-        mxv = fmaxf(mxv, v);
-      }
+    COL_STATS(old, MI, jn, s1, s2, mn, mxv);
     rows_reduce4(s1, s2, mn, mxv);
     if (lane < 16) {
       const int col = (wn * 4 + jn) * 16 + lane;
@@ -1195,13 +1204,7 @@ __global__ __launch_bounds__(512, 2) void conv_l2a_kernel(const ConvK a, unsigne
   // kernel -- made every CU of the chip store in the same two of eight steps: those steps took twice as long, the stores
   // queueing at HBM's write rate.)
   // row block i of the pending tile -> the wave's transposition buffer
-  auto ep_Tw = [&](int i) {
-#pragma unroll
-    for (int jn = 0; jn < 4; ++jn)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) tr[(4 * (lane >> 4) + e) * TRS + jn * 16 + (lane & 15)] = old[i][jn][e];
-    __builtin_amdgcn_wave_barrier();
-  };
+  auto ep_Tw = [&](int i) { TRANSPOSE_WRITE(tr, old[i], lane); };
   // chunk g: out of the buffer, unscaled, T counted operations (rows past M / columns past Cout: out of range, dropped)
   auto ep_chunk = [&](int g) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1405,7 +1408,7 @@ __global__ __launch_bounds__(256) void conv_l2_fixup_kernel(const ConvK a, int G
   constexpr int C4 = BN / 4;      // float4 columns of a tile row
   constexpr int RG = 256 / C4;    // rows covered by the workgroup (one element group per thread)
   constexpr int SUB = BM / RG;    // sub-blocks per tile
-  __shared__ f32x4 red[4][256];
+  __shared__ f32x4 red[3][256];
   __shared__ int piece[1024];
   __shared__ int wave_count[4];
   const OndaConv& c = a.c;
@@ -1428,11 +1431,11 @@ __global__ __launch_bounds__(256) void conv_l2_fixup_kernel(const ConvK a, int G
                         : nullptr;
   if (vs == ve) {  // computed whole by one workgroup: its own epilogue ran; the extra statistic rows are identities
     if (srow && sub != 0 && rg == 0 && vn) {
-      *reinterpret_cast<f32x4*>(srow) = f32x4{0.f, 0.f, 0.f, 0.f};
-      *reinterpret_cast<f32x4*>(srow + c.Cout) = f32x4{0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<f32x4*>(srow) = splat4(0.f);
+      *reinterpret_cast<f32x4*>(srow + c.Cout) = splat4(0.f);
       if (SR == 4) {
-        *reinterpret_cast<f32x4*>(srow + 2 * c.Cout) = f32x4{3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};
-        *reinterpret_cast<f32x4*>(srow + 3 * c.Cout) = f32x4{-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+        *reinterpret_cast<f32x4*>(srow + 2 * c.Cout) = splat4(STAT_MIN_ID);
+        *reinterpret_cast<f32x4*>(srow + 3 * c.Cout) = splat4(STAT_MAX_ID);
       }
     }
     return;
@@ -1470,66 +1473,38 @@ __global__ __launch_bounds__(256) void conv_l2_fixup_kernel(const ConvK a, int G
     for (int j = 0; j < 8; ++j) v += p + j < nvalid ? part[j] : zero;
   }
   const int m = tile_m * BM + row;
+  const bool live = m < a.M && vn;
+  // (not FUSED, below: this kernel has always rounded the product with the scale before it adds the shift.  1 and 0 stand in
+  //  for an absent scale or shift: a launch with a scale and NO shift then stores +0 where the product is an exact -0)
+  f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = zero;
+  if (live && a.scale) sc = *reinterpret_cast<const f32x4*>(a.scale + n);
+  if (live && a.shift) sh = *reinterpret_cast<const f32x4*>(a.shift + n);
   float mx = 0.f;
-  if (a.yl != nullptr) {  // limb-plane output (l2_epilogue_limbs): same bound, same scale, same arithmetic
-    const float bound = limb_out_bound(a);
-    const float so = scale_from(bound).s;
-    if (t == 0) a.ybound[(blockIdx.x & (ONDA_AMAX_SLOTS - 1)) * AMAX_STRIDE] = bound;
-    const float ri = a.resl != nullptr ? scale_of(a.res_amax).inv : 0.f;
-    if (m < a.M && vn) {
-      f32x4 o = v;
-      if (a.scale) o *= *reinterpret_cast<const f32x4*>(a.scale + n);
-      if (a.shift) o += *reinterpret_cast<const f32x4*>(a.shift + n);
+  if (a.yl != nullptr) {  // limb-plane output
+    const LimbOutScale lo = limb_out_scale(a, t);
+    if (live) {
+      u32x2 q1 = {0u, 0u}, q2 = {0u, 0u}, l1, l2;
       if (a.resl != nullptr) {
         const _Float16* p = a.resl + limb_at((size_t)m, n, c.ldr);
-        const u32x2 q1 = *reinterpret_cast<const u32x2*>(p), q2 = *reinterpret_cast<const u32x2*>(p + LIMB2_OFS);
-        o += join4(q1, q2) * ri;
+        q1 = *reinterpret_cast<const u32x2*>(p);
+        q2 = *reinterpret_cast<const u32x2*>(p + LIMB2_OFS);
       }
-      if (c.relu) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = fmaxf(o[j], 0.f);
-      }
-      mx = fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3])));
-      u32x2 l1, l2;
-      const f32x4 w = o * so;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const LimbPair p = split2(w[2 * h], w[2 * h + 1]);
-        l1[h] = p.l1;
-        l2[h] = p.l2;
-      }
+      mx = max_abs4(mx, limb_out4<false>(lo, v, sc, sh, a.resl != nullptr, q1, q2, c.relu, l1, l2));
       _Float16* dst = a.yl + limb_at((size_t)m, n, c.ldy);
       *reinterpret_cast<u32x2*>(dst) = l1;
       *reinterpret_cast<u32x2*>(dst + LIMB2_OFS) = l2;
     }
-    if (a.amax != nullptr) amax_update_block(a.amax, mx, reinterpret_cast<float*>(&red[0][0]));
-    return;
+  } else if (live) {
+    const f32x4 o = conv_out4<false>(v, sc, sh, a.res ? reinterpret_cast<const f32x4*>(a.res + (size_t)m * c.ldr + n) : nullptr, c.relu);
+    *reinterpret_cast<f32x4*>(a.y + (dense_out(c) ? (size_t)m : out_row(c, m)) * c.ldy + n) = o;
+    mx = max_abs4(mx, o);
   }
-  if (m < a.M && vn) {
-    f32x4 o = v;
-    if (a.scale) o *= *reinterpret_cast<const f32x4*>(a.scale + n);
-    if (a.shift) o += *reinterpret_cast<const f32x4*>(a.shift + n);
-    if (a.res) o += *reinterpret_cast<const f32x4*>(a.res + (size_t)m * c.ldr + n);
-    if (c.relu) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = fmaxf(o[j], 0.f);
-    }
-    size_t orow = m;
-    if (!(c.out_os == 1 && c.Hf == c.Ho && c.Wf == c.Wo)) {
-      const int wo = m % c.Wo, tq = m / c.Wo;
-      const int ho = tq % c.Ho, b = tq / c.Ho;
-      orow = ((size_t)b * c.Hf + (size_t)ho * c.out_os) * c.Wf + (size_t)wo * c.out_os;
-    }
-    *reinterpret_cast<f32x4*>(a.y + orow * c.ldy + n) = o;
-    mx = fmaxf(fmaxf(mx, fmaxf(fabsf(o[0]), fabsf(o[1]))), fmaxf(fabsf(o[2]), fabsf(o[3])));
-  }
-  if (a.amax != nullptr) amax_update_block(a.amax, mx, reinterpret_cast<float*>(&red[0][0]));
-  if (a.stats != nullptr) {
+  if (a.amax != nullptr) tile_amax_publish(a.amax, mx, reinterpret_cast<float*>(&red[0][0]));
+  if (a.stats != nullptr) {  // (never with limb planes)
     __syncthreads();
     red[0][t] = v;
     red[1][t] = v * v;
     red[2][t] = v;
-    red[3][t] = v;
     __syncthreads();
     if (rg == 0 && vn) {
       f32x4 s1 = red[0][t], s2 = red[1][t], mn = v, mxv = v;

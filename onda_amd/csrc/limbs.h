@@ -90,10 +90,10 @@ __device__ __forceinline__ LimbPair split2(float a, float b) {
   return LimbPair{p, cvt2h_rest(a, b, p)};
 }
 // The widths the kernels use, on top of the pair.  They fill local vectors and assign them whole (element writes through a
-// reference come out as other shuffles).  Three sites call split2 in a loop of their own instead -- the stem's patch kernel and
-// the stream-K fixup's limb output (conv_l2.hip), max-pool (pointwise.hip): a helper is simplified on its own before it is
-// inlined, its loop is gone by then, and the instruction order of those three kernels depends on the loop being theirs (same
-// values, other assembly: docs/experiments.md, "The limb format, once").
+// reference come out as other shuffles).  Two sites call split2 in a loop of their own instead -- the stem's patch kernel
+// (conv_l2.hip) and max-pool (pointwise.hip): a helper is simplified on its own before it is inlined, its loop is gone by
+// then, and the instruction order of those two kernels depends on the loop being theirs (same values, other assembly:
+// docs/experiments.md, "The limb format, once").
 // 4 scaled floats -> 4 + 4 f16 (8 bytes per limb)
 __device__ __forceinline__ void split4(const f32x4 v, u32x2& l1, u32x2& l2) {
   u32x2 a, b;

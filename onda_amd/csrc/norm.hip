@@ -84,11 +84,6 @@ __device__ __forceinline__ f32x4 relu_mask(f32x4 g, const f32x4 ov) {
   return g;
 }
 
-// Running max|v| of an apply pass (folded into the tensor's slots by amax_update_block at the end of the kernel).
-__device__ __forceinline__ float max_abs4(float mx, const f32x4 v) {
-  return fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
-}
-
 // One-pass statistics finished in double: sum, sum of squares over `count` values.
 struct Moments {
   double mean, var, rstd;
@@ -232,7 +227,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     mx = max_abs4(mx, v);
   }
   __shared__ float amax_red[4];
-  if (amax != nullptr) amax_update_block(amax, mx, amax_red);
+  if (amax != nullptr) tile_amax_publish(amax, mx, amax_red);
 }
 
 __global__ void bn_fold_kernel(const float* gamma, const float* beta, const float* rmean, const float* rvar, float eps,
@@ -280,7 +275,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     mx = max_abs4(mx, v);
   }
   __shared__ float amax_red[4];
-  if (amax != nullptr) amax_update_block(amax, mx, amax_red);
+  if (amax != nullptr) tile_amax_publish(amax, mx, amax_red);
 }
 
 // ---- GroupNorm --------------------------------------------------------------------------
@@ -350,7 +345,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
   }
   // the output feeds a convolution (directly, or through the SE gate): leave max|out| behind
   __shared__ float amax_red[4];
-  if (amax != nullptr) amax_update_block(amax, mx, amax_red);
+  if (amax != nullptr) tile_amax_publish(amax, mx, amax_red);
 }
 
 // AB[b][2][C] -> dgamma/dbeta and the per-(image, group) sums the dx formula needs
@@ -408,7 +403,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
     mx = max_abs4(mx, v);
   }
   __shared__ float amax_red[4];
-  if (amax != nullptr) amax_update_block(amax, mx, amax_red);
+  if (amax != nullptr) tile_amax_publish(amax, mx, amax_red);
 }
 
 __global__ __launch_bounds__(256) void colsum_finalize_kernel(const float* __restrict__ partials, int chunks, int B,

@@ -309,7 +309,7 @@ __device__ __forceinline__ void bn_finalize_block(const BnFinalizeArgs& a, const
   if (res_amax != nullptr) bound += amax_read(res_amax);
   bound *= 1.0000005f;  // the apply pass rounds differently; the scale leaves a factor 2 of headroom anyway
   __shared__ float red[4];
-  // one atomic per workgroup, slot by (bx, g) (amax_update_block takes blockIdx.x, which is something else in the fused launch)
+  // one atomic per workgroup, slot by (bx, g) (tile_amax_publish takes blockIdx.x, which is something else in the fused launch)
   float m = wave_max(bound);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
