@@ -242,6 +242,38 @@ int onda_bn_bwd_l2(const float* dout, const void* out, int64_t out_plane, const 
                    const float* gamma, const float* xhat_amax, void* dx, int64_t dx_plane, float* dx_amax, float* dres, float* ws,
                    int64_t M, int C, int relu, const uint8_t* relu_mask, int64_t split, int fuse_sums, onda_stream_t s);
 
+/* ---- a PAIR of train-mode BatchNorms whose outputs meet in one add: the first block of a ResNet layer,
+ *   out = [relu](BN_a(xa) + BN_b(xb))   (a: the block's last conv, b: the shortcut conv; deeplabv2.py:53-68).
+ * As two onda_bn_* calls the shortcut's result is written as limb rows only to be read back by the other apply pass, and the
+ * masked gradient as fp32 only to be read back twice.  Here each direction walks the tensors once: forward reads xa and xb and
+ * writes out (12 instead of 20 bytes per element), backward reads dout, xa and xb twice and writes the two conv gradients (32
+ * instead of 44).  Each term is evaluated as the single kernels evaluate it, then one fp32 add.
+ * One side = one BatchNorm: x its conv output (dense [M][C]), partials[tiles][4][C] that conv's statistics (tile_rows GEMM
+ * rows per partial row), mean / invstd / xhat_amax [groups][C] (written by the forward call, read by the backward call),
+ * running buffers (NULL: not tracked) and momentum, frozen gamma / beta; backward only: dx (limb rows [M][C]) and dx_amax
+ * (ONDA_AMAX_FLOATS zeroed floats).  Row groups (split, run_group) as above, the same split for both sides.
+ * fwd: two launches (statistics of both sides and the bound of max|out| -- per channel the SUM of the two sides' bounds, which
+ *   is why both meet in one workgroup -- then the apply pass); out limb rows [M][C] under out_amax (zeroed), relu_mask optional.
+ * bwd: three launches (chunk partials of sum g, sum g*xhat_a, sum g*xhat_b, max|g| with g = dout * mask, fixed order; their
+ *   reduction with both dx bounds; the apply pass).  ws: onda_bn_pair_bwd_l2_ws(M, C) floats.  relu != 0 needs relu_mask. */
+typedef struct OndaBnSide {
+  const float* x;
+  const float* partials;
+  int tiles, tile_rows;
+  float *mean, *invstd, *xhat_amax;
+  float *running_mean, *running_var;
+  int64_t* nbt;
+  float momentum;
+  const float *gamma, *beta;
+  void* dx;
+  float* dx_amax;
+} OndaBnSide;
+int onda_bn_pair_fwd_l2(const OndaBnSide* a, const OndaBnSide* b, float eps, int relu, void* out, float* out_amax, int64_t M, int C,
+                        uint8_t* relu_mask, int64_t split, int run_group, onda_stream_t s);
+int64_t onda_bn_pair_bwd_l2_ws(int64_t M, int C);
+int onda_bn_pair_bwd_l2(const float* dout, const uint8_t* relu_mask, const OndaBnSide* a, const OndaBnSide* b, float* ws, int64_t M,
+                        int C, int relu, int64_t split, onda_stream_t s);
+
 /* onda_conv2d_wgrad slabs with both operands pre-split: [pixel][channel] limb planes in, LDS-DMA + transposed LDS reads
  * (ds_read_b64_tr_b16), tiles of 256 x 128 or 128 x 128 (output x input channels) per tap and pixel range.
  * The 256 x 128 kernel reads the input pixel of every (tap, output pixel) from a table per convolution GEOMETRY (input and

@@ -31,6 +31,13 @@ class OndaLimbOut(Structure):
                 ("xtrue", c_void_p), ("res", c_void_p), ("res_plane", c_int64), ("res_amax", c_void_p), ("res_true", c_void_p)]
 
 
+class OndaBnSide(Structure):
+    _fields_ = [("x", c_void_p), ("partials", c_void_p), ("tiles", c_int), ("tile_rows", c_int), ("mean", c_void_p),
+                ("invstd", c_void_p), ("xhat_amax", c_void_p), ("running_mean", c_void_p), ("running_var", c_void_p),
+                ("nbt", c_void_p), ("momentum", c_float), ("gamma", c_void_p), ("beta", c_void_p), ("dx", c_void_p),
+                ("dx_amax", c_void_p)]
+
+
 class OndaSgdEntry(Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("buf", c_void_p), ("n", c_int64), ("lr", c_float),
                 ("times", c_int), ("fresh", c_int), ("first_block", c_int)]
@@ -95,6 +102,9 @@ SIGNATURES = {
     "onda_bn_bwd_l2_ws": (L, [L, I]),
     "onda_bn_train_l2": (I, [P, P, I, F, P, P, P, P, P, F, P, P, P, P, I, P, P, P, L, I, P, L, I, I, P]),
     "onda_bn_bwd_l2": (I, [P, P, L, P, P, P, P, P, P, L, P, P, P, L, I, I, P, L, I, P]),
+    "onda_bn_pair_fwd_l2": (I, [POINTER(OndaBnSide), POINTER(OndaBnSide), F, I, P, P, L, I, P, L, I, P]),
+    "onda_bn_pair_bwd_l2_ws": (L, [L, I]),
+    "onda_bn_pair_bwd_l2": (I, [P, P, POINTER(OndaBnSide), POINTER(OndaBnSide), P, L, I, I, L, P]),
     "onda_conv2d_wgrad": (I, [P, P, P, I, I, POINTER(OndaConv), P]),
     "onda_wgrad_reduce": (I, [P, P, I, I, I, I, I, I, I, I, P]),
     "onda_pack_weight_fwd": (I, [P, P, I, I, I, I, I, P]),

@@ -200,17 +200,18 @@ struct BnFinalizeArgs {
   const float* y;
   int ldy;
 };
-// one workgroup (256 threads) = 16 channels `bx` of row group `g`
-__device__ __forceinline__ void bn_finalize_block(const BnFinalizeArgs& a, const int bx, const int g) {
+// one workgroup (256 threads) = 16 channels `bx` of row group `g`: everything of the finalize pass but the bound of max|out|.
+// f_lo / f_hi: the affine images of the channel's extrema in thread c < 16 (zero in every other thread and past C); the
+// output of the channel lies between them, in either order.  Shared arrays are reused by the next call: barrier in between.
+__device__ __forceinline__ void bn_finalize_channel(const BnFinalizeArgs& a, const int bx, const int g, float& f_lo, float& f_hi) {
   const float* __restrict__ partials = a.partials;
-  const int tiles = a.tiles, C = a.C, relu = a.relu, bm = a.bm, run_group = a.run_group, ldy = a.ldy;
+  const int tiles = a.tiles, C = a.C, bm = a.bm, run_group = a.run_group, ldy = a.ldy;
   double count = a.count;
   const float eps = a.eps, momentum = a.momentum;
-  float *mean = a.mean, *invstd = a.invstd, *rmean = a.rmean, *rvar = a.rvar, *xhat_amax = a.xhat_amax, *out_amax = a.out_amax;
+  float *mean = a.mean, *invstd = a.invstd, *rmean = a.rmean, *rvar = a.rvar, *xhat_amax = a.xhat_amax;
   int64_t* nbt = a.nbt;
   const float* __restrict__ gamma = a.gamma;
   const float* __restrict__ beta = a.beta;
-  const float* __restrict__ res_amax = a.res_amax;
   const float* __restrict__ y = a.y;
   const long long split = a.split;
   if (bx == 0 && g == 0 && threadIdx.x == 0 && nbt) *nbt += 1;
@@ -260,7 +261,7 @@ __device__ __forceinline__ void bn_finalize_block(const BnFinalizeArgs& a, const
   reduce_rows16<4, 2, true>(partials + (size_t)row0 * 4 * C, nrows, C, bx * 16, sum, ext, rescan ? nrows - sub1 : nrows,
                             rescan ? tiles_m - 1 - row0 : -1);
   const int ch = bx * 16 + threadIdx.x;
-  float bound = 0.f;
+  f_lo = f_hi = 0.f;
   if (threadIdx.x < 16 && ch < C) {
     if (rescan) {
 #pragma unroll
@@ -295,8 +296,8 @@ __device__ __forceinline__ void bn_finalize_block(const BnFinalizeArgs& a, const
     const float muf = (float)mu, is = (float)(1.0 / sqrt(var + (double)eps));
     const float lo = (ext[0] - muf) * is, hi = (ext[1] - muf) * is;
     const float gm = gamma[ch], b = beta[ch];
-    const float f_lo = lo * gm + b, f_hi = hi * gm + b;
-    bound = relu ? fmaxf(0.f, fmaxf(f_lo, f_hi)) : fmaxf(fabsf(f_lo), fabsf(f_hi));  // behind a ReLU only the positive side counts
+    f_lo = lo * gm + b;
+    f_hi = hi * gm + b;
     mean[g * C + ch] = muf;
     invstd[g * C + ch] = is;
     xhat_amax[g * C + ch] = fmaxf(fabsf(lo), fabsf(hi));
@@ -306,10 +307,10 @@ __device__ __forceinline__ void bn_finalize_block(const BnFinalizeArgs& a, const
       rvar[ch] = (1.f - momentum) * rvar[ch] + momentum * (float)unbiased;
     }
   }
-  if (res_amax != nullptr) bound += amax_read(res_amax);
-  bound *= 1.0000005f;  // the apply pass rounds differently; the scale leaves a factor 2 of headroom anyway
+}
+// one atomic per workgroup, slot by (bx, g) (tile_amax_publish takes blockIdx.x, which is something else in the fused launch)
+__device__ __forceinline__ void bn_bound_publish(float bound, float* out_amax, const int bx, const int g) {
   __shared__ float red[4];
-  // one atomic per workgroup, slot by (bx, g) (tile_amax_publish takes blockIdx.x, which is something else in the fused launch)
   float m = wave_max(bound);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
@@ -319,7 +320,31 @@ __device__ __forceinline__ void bn_finalize_block(const BnFinalizeArgs& a, const
       atomicMax(reinterpret_cast<unsigned*>(out_amax) + ((bx + 7 * g) & (ONDA_AMAX_SLOTS - 1)) * AMAX_STRIDE, __float_as_uint(m));
   }
 }
+__device__ __forceinline__ void bn_finalize_block(const BnFinalizeArgs& a, const int bx, const int g) {
+  float f_lo, f_hi;
+  bn_finalize_channel(a, bx, g, f_lo, f_hi);
+  float bound = a.relu ? fmaxf(0.f, fmaxf(f_lo, f_hi)) : fmaxf(fabsf(f_lo), fabsf(f_hi));  // behind a ReLU only the positive side counts
+  if (a.res_amax != nullptr) bound += amax_read(a.res_amax);
+  bound *= 1.0000005f;  // the apply pass rounds differently; the scale leaves a factor 2 of headroom anyway
+  bn_bound_publish(bound, a.out_amax, bx, g);
+}
 __global__ __launch_bounds__(256) void bn_finalize_l2_kernel(const BnFinalizeArgs a) { bn_finalize_block(a, blockIdx.x, blockIdx.y); }
+
+// The finalize pass of a PAIR of BatchNorms whose outputs are added (out = [relu](BN_a + BN_b)): both sides' statistics by the
+// same workgroup, because the bound of the sum is per channel -- [lo_a + lo_b, hi_a + hi_b] holds the channel's output -- and
+// only then a maximum over channels; two separately published maxima could only be added, the worst channel of one to the
+// worst of the other.  relu / out_amax are taken from `a`.
+__global__ __launch_bounds__(256) void bn_finalize_pair_l2_kernel(const BnFinalizeArgs a, const BnFinalizeArgs b) {
+  float lo_a, hi_a, lo_b, hi_b;
+  bn_finalize_channel(a, blockIdx.x, blockIdx.y, lo_a, hi_a);
+  __syncthreads();  // (the shared arrays of the first call are read by its threads < 16 to the end)
+  bn_finalize_channel(b, blockIdx.x, blockIdx.y, lo_b, hi_b);
+  const float lo = fminf(lo_a, hi_a) + fminf(lo_b, hi_b), hi = fmaxf(lo_a, hi_a) + fmaxf(lo_b, hi_b);
+  float bound = a.relu ? fmaxf(0.f, hi) : fmaxf(fabsf(lo), fabsf(hi));
+  // the apply pass rounds differently, and its roundings are relative to the TERMS, which may cancel in the sum
+  bound += 1.0e-6f * (fmaxf(fabsf(lo_a), fabsf(hi_a)) + fmaxf(fabsf(lo_b), fabsf(hi_b)));
+  bn_bound_publish(bound, a.out_amax, blockIdx.x, blockIdx.y);
+}
 
 // out limbs = [relu]( (x - mean)*invstd*gamma + beta [+ residual limbs] ), 8 channels per thread.
 // group1_at > 0: two row groups -- 8-channel items [0, group1_at) normalise with the statistics at mean / invstd, the others with
@@ -408,6 +433,75 @@ __global__ __launch_bounds__(256) void bn_apply_l2_kernel(const float* __restric
       r2 = *reinterpret_cast<const u32x4*>(res + lofs(e) + LIMB2_OFS);
     }
     one(e, LD4(x + e * 8), LD4(x + e * 8 + 4), r1, r2, __ballot(1) == ~0ull);
+  }
+}
+
+// out limbs = [relu]( BN_a(xa) + BN_b(xb) ), 8 channels per thread: bn_apply_l2_kernel with a second normalised term in the
+// place of the residual limbs -- the shortcut BatchNorm of a downsample block is never written and read back.  Each term is the
+// single kernel's expression, then one fp32 add.
+// Two row groups: a thread's items e0, e0 + stride, ... cross group1_at at most once, so the walk is cut there and ONE set of
+// statistics is live at a time (two BatchNorms x two groups, selected per item, would be 80 registers of constants).
+struct BnPairSide {
+  const float *x, *mean, *invstd, *gamma, *beta;
+};
+__global__ __launch_bounds__(256) void bn_apply_pair_l2_kernel(const BnPairSide sa, const BnPairSide sb, _Float16* __restrict__ out,
+                                                               const float* __restrict__ out_amax, size_t total8, int C, int relu,
+                                                               unsigned char* __restrict__ mask, size_t group1_at) {
+  const float* __restrict__ xa = sa.x;
+  const float* __restrict__ xb = sb.x;
+  const int c8 = C / 8;
+  const float so = scale_of(out_amax).s;
+  const size_t e0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int col = (int)(e0 % c8) * 8;  // fixed per thread (see bn_apply_l2_kernel)
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const size_t lcol = limb_at(0, col, C);
+  auto lofs = [&](size_t e) { return (size_t)((unsigned)e / (unsigned)c8) * 2 * (size_t)C + lcol; };  // (items < 2^32: 32-bit division)
+  const size_t cut = group1_at > 0 ? group1_at : total8;
+  size_t e = e0;
+#pragma unroll 1
+  for (int g = 0; g < 2; ++g) {
+    const size_t end = g == 0 ? cut : total8;
+    if (e >= end) continue;
+    const int go = g * C + col;  // (group 1 has items only with two row groups)
+    const f32x4 ga0 = LD4(sa.gamma + col), ga1 = LD4(sa.gamma + col + 4), gb0 = LD4(sb.gamma + col), gb1 = LD4(sb.gamma + col + 4);
+    const f32x4 sca0 = LD4(sa.invstd + go) * ga0, sca1 = LD4(sa.invstd + go + 4) * ga1;
+    const f32x4 scb0 = LD4(sb.invstd + go) * gb0, scb1 = LD4(sb.invstd + go + 4) * gb1;
+    const f32x4 mua0 = LD4(sa.mean + go), mua1 = LD4(sa.mean + go + 4), mub0 = LD4(sb.mean + go), mub1 = LD4(sb.mean + go + 4);
+    const f32x4 bea0 = LD4(sa.beta + col), bea1 = LD4(sa.beta + col + 4), beb0 = LD4(sb.beta + col), beb1 = LD4(sb.beta + col + 4);
+    auto one = [&](size_t i, f32x4 a0, f32x4 a1, f32x4 b0, f32x4 b1, bool whole) {
+      const f32x4 ta0 = (a0 - mua0) * sca0 + bea0, ta1 = (a1 - mua1) * sca1 + bea1;
+      const f32x4 tb0 = (b0 - mub0) * scb0 + beb0, tb1 = (b1 - mub1) * scb1 + beb1;
+      f32x4 v0 = ta0 + tb0, v1 = ta1 + tb1;
+      if (mask) {  // [out > 0], one bit per element (byte i = the 8 channels of this item)
+        unsigned bits = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bits |= (v0[j] > 0.f ? 1u << j : 0u) | (v1[j] > 0.f ? 16u << j : 0u);
+        mask[i] = (unsigned char)bits;
+      }
+      if (relu) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          v0[j] = fmaxf(v0[j], 0.f);
+          v1[j] = fmaxf(v1[j], 0.f);
+        }
+      }
+      u32x4 l1, l2;
+      split8(v0 * so, v1 * so, l1, l2);
+      store_limb_lines(out + lofs(i), l1, l2, whole);
+    };
+    // two independent items per iteration: all loads of both are issued before the first is used
+    for (; e + stride < end; e += 2 * stride) {
+      const size_t f = e + stride;
+      const f32x4 a0 = LD4S(xa + e * 8), a1 = LD4S(xa + e * 8 + 4), b0 = LD4S(xb + e * 8), b1 = LD4S(xb + e * 8 + 4);
+      const f32x4 c0 = LD4S(xa + f * 8), c1 = LD4S(xa + f * 8 + 4), d0 = LD4S(xb + f * 8), d1 = LD4S(xb + f * 8 + 4);
+      const bool whole = __ballot(1) == ~0ull;  // (the loop condition holds for every lane that is in here)
+      one(e, a0, a1, b0, b1, whole);
+      one(f, c0, c1, d0, d1, whole);
+    }
+    if (e < end) {
+      one(e, LD4S(xa + e * 8), LD4S(xa + e * 8 + 4), LD4S(xb + e * 8), LD4S(xb + e * 8 + 4), __ballot(1) == ~0ull);
+      e += stride;
+    }
   }
 }
 
@@ -604,6 +698,164 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_l2_kernel(const float* __res
   }
 }
 
+// ---- backward of the pair: out = relu(BN_a(xa) + BN_b(xb)) hands the SAME g = dout * [out > 0] to both BatchNorms --------------
+// pass 1: one walk for both -- sum g, sum g * xhat_a, sum g * xhat_b, max|g| per chunk and channel ([chunks][4][C]); same chunk
+// plan, same fixed order as bn_bwd_reduce_l2_kernel; g is never written
+__global__ __launch_bounds__(256) void bn_bwd_reduce_pair_l2_kernel(const float* __restrict__ dout, const float* __restrict__ xa,
+                                                                    const float* __restrict__ xb, const float* __restrict__ mean_a,
+                                                                    const float* __restrict__ invstd_a, const float* __restrict__ mean_b,
+                                                                    const float* __restrict__ invstd_b, int64_t M, int C, int relu, int cx,
+                                                                    int64_t rows_per_chunk, float* __restrict__ partials,
+                                                                    const unsigned char* __restrict__ mask, int64_t split, int chunks0) {
+  __shared__ f32x4 red[4][256];
+  const int t = threadIdx.x;
+  const int ry_n = 256 / cx;
+  const int tx = t % cx, ty = t / cx;
+  const int col = (blockIdx.x * cx + tx) * 4;
+  const int chunk = blockIdx.y;
+  const bool second = split > 0 && chunk >= chunks0;
+  const int64_t r0 = second ? split + (int64_t)(chunk - chunks0) * rows_per_chunk : (int64_t)chunk * rows_per_chunk;
+  const int64_t r1 = min(split > 0 && !second ? split : M, r0 + rows_per_chunk);
+  f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f}, s3 = {0.f, 0.f, 0.f, 0.f}, s4 = {0.f, 0.f, 0.f, 0.f};
+  if (col < C) {
+    const int gofs = second ? C : 0;
+    const f32x4 mua = LD4(mean_a + gofs + col), isa = LD4(invstd_a + gofs + col);
+    const f32x4 mub = LD4(mean_b + gofs + col), isb = LD4(invstd_b + gofs + col);
+    for (int64_t r = r0 + ty; r < r1; r += ry_n) {
+      const size_t o = (size_t)r * C + col;
+      f32x4 g = LD4(dout + o);
+      const f32x4 va = LD4(xa + o), vb = LD4(xb + o);
+      if (relu) g = relu_mask4(nullptr, mask, o, g, C);
+      s1 += g;
+      s2 += g * ((va - mua) * isa);
+      s3 += g * ((vb - mub) * isb);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s4[j] = fmaxf(s4[j], fabsf(g[j]));
+    }
+  }
+  red[0][t] = s1;
+  red[1][t] = s2;
+  red[2][t] = s3;
+  red[3][t] = s4;
+  __syncthreads();
+  if (ty == 0 && col < C) {
+    for (int y = 1; y < ry_n; ++y) {
+      s1 += red[0][y * cx + tx];
+      s2 += red[1][y * cx + tx];
+      s3 += red[2][y * cx + tx];
+      const f32x4 o4 = red[3][y * cx + tx];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s4[j] = fmaxf(s4[j], o4[j]);
+    }
+    float* dst = partials + ((size_t)chunk * 4) * C + col;
+    *reinterpret_cast<f32x4*>(dst) = s1;
+    *reinterpret_cast<f32x4*>(dst + C) = s2;
+    *reinterpret_cast<f32x4*>(dst + 2 * C) = s3;
+    *reinterpret_cast<f32x4*>(dst + 3 * C) = s4;
+  }
+}
+
+// pass 2: chunk partials [chunks][4][C] -> sums[groups][3][C] (sum g, sum g * xhat_a, sum g * xhat_b) and bn_bwd_sums_block's
+// bound of max|dx| for each side into that side's own dx_amax; 16 channels per workgroup, blockIdx.y = row group
+struct BnBwdSumsSide {
+  const float *gamma, *invstd, *xhat_amax;
+  float* dx_amax;
+};
+struct BnBwdSumsPairArgs {
+  const float* partials;
+  int chunks, C;
+  double inv_m0, inv_m1;
+  BnBwdSumsSide a, b;
+  float* sums;
+  int chunks0, groups;
+};
+__global__ __launch_bounds__(256) void bn_bwd_sums_pair_l2_kernel(const BnBwdSumsPairArgs p) {
+  const int C = p.C, bx = blockIdx.x, g = blockIdx.y;
+  const int row0 = g == 0 ? 0 : p.chunks0, nrows = p.groups == 1 ? p.chunks : (g == 0 ? p.chunks0 : p.chunks - p.chunks0);
+  const double inv_m = g == 0 ? p.inv_m0 : p.inv_m1;
+  double sum[3];
+  float ext[1];
+  reduce_rows16<4, 3, false>(p.partials + (size_t)row0 * 4 * C, nrows, C, bx * 16, sum, ext, nrows);
+  const int ch = bx * 16 + threadIdx.x;
+  float bound_a = 0.f, bound_b = 0.f;
+  if (threadIdx.x < 16 && ch < C) {
+#pragma unroll
+    for (int v = 0; v < 3; ++v) p.sums[(g * 3 + v) * C + ch] = (float)sum[v];
+    const float gmax = ext[0], m1 = (float)(fabs(sum[0]) * inv_m);
+    bound_a = fabsf(p.a.gamma[ch] * p.a.invstd[g * C + ch]) * (gmax + m1 + p.a.xhat_amax[g * C + ch] * (float)(fabs(sum[1]) * inv_m));
+    bound_b = fabsf(p.b.gamma[ch] * p.b.invstd[g * C + ch]) * (gmax + m1 + p.b.xhat_amax[g * C + ch] * (float)(fabs(sum[2]) * inv_m));
+  }
+  bn_bound_publish(bound_a * 1.000001f, p.a.dx_amax, bx, g);
+  __syncthreads();  // (the publishing step's shared words)
+  bn_bound_publish(bound_b * 1.000001f, p.b.dx_amax, bx, g);
+}
+
+// pass 3: both conv gradients from one walk -- reads dout, the mask, xa and xb once, writes dx_a and dx_b as limb rows under
+// their own scales; each is bn_bwd_apply_l2_kernel's expression but for one association (below).  The walk is cut at group1_at
+// (see bn_apply_pair_l2_kernel); mean(g) is one set of registers for both sides.  128 registers, no scratch: the occupancy of
+// the single kernel (120).
+struct BnBwdPairSide {
+  const float *x, *mean, *invstd, *gamma;
+  _Float16* dx;
+  const float* dx_amax;
+};
+__global__ __launch_bounds__(256) void bn_bwd_apply_pair_l2_kernel(const float* __restrict__ dout, const BnBwdPairSide sa,
+                                                                   const BnBwdPairSide sb, const float* __restrict__ sums, size_t total8,
+                                                                   int C, float inv_m0, float inv_m1, int relu,
+                                                                   const unsigned char* __restrict__ mask, size_t group1_at) {
+  const float* __restrict__ xa = sa.x;
+  const float* __restrict__ xb = sb.x;
+  _Float16* __restrict__ dxa = sa.dx;
+  _Float16* __restrict__ dxb = sb.dx;
+  const int c8 = C / 8;
+  const float sda = scale_of(sa.dx_amax).s, sdb = scale_of(sb.dx_amax).s;
+  const size_t e0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int col = (int)(e0 % c8) * 8;  // fixed per thread (see bn_apply_l2_kernel)
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const size_t lcol = limb_at(0, col, C);
+  const size_t cut = group1_at > 0 ? group1_at : total8;
+  size_t e = e0;
+#pragma unroll 1
+  for (int g = 0; g < 2; ++g) {
+    const size_t end = g == 0 ? cut : total8;
+    if (e >= end) continue;
+    const float im = g == 0 ? inv_m0 : inv_m1;
+    // (xhat * mean(g * xhat) as (x - mean) * (invstd * mean(g * xhat)): invstd need not stay in registers -- 128 instead of 144)
+    f32x4 m1[2], mua[2], gia[2], m2a[2], mub[2], gib[2], m2b[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int cc = col + 4 * h, go = g * C + cc;
+      const f32x4 isa = LD4(sa.invstd + go), isb = LD4(sb.invstd + go);
+      m1[h] = LD4(sums + (size_t)(g * 3) * C + cc) * im;
+      mua[h] = LD4(sa.mean + go);
+      gia[h] = LD4(sa.gamma + cc) * isa;
+      m2a[h] = isa * (LD4(sums + (size_t)(g * 3 + 1) * C + cc) * im);
+      mub[h] = LD4(sb.mean + go);
+      gib[h] = LD4(sb.gamma + cc) * isb;
+      m2b[h] = isb * (LD4(sums + (size_t)(g * 3 + 2) * C + cc) * im);
+    }
+    for (; e < end; e += stride) {
+      f32x4 va[2], vb[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const size_t o = e * 8 + 4 * h;
+        f32x4 gr = LD4S(dout + o);
+        const f32x4 pa = LD4S(xa + o), pb = LD4S(xb + o);
+        if (relu) gr = relu_mask4(nullptr, mask, o, gr, C);
+        va[h] = gia[h] * (gr - m1[h] - (pa - mua[h]) * m2a[h]);
+        vb[h] = gib[h] * (gr - m1[h] - (pb - mub[h]) * m2b[h]);
+      }
+      const bool whole = __ballot(1) == ~0ull;
+      const size_t lo = (size_t)((unsigned)e / (unsigned)c8) * 2 * (size_t)C + lcol;
+      u32x4 l1, l2;
+      split8(va[0] * sda, va[1] * sda, l1, l2);
+      store_limb_lines(dxa + lo, l1, l2, whole);
+      split8(vb[0] * sdb, vb[1] * sdb, l1, l2);
+      store_limb_lines(dxb + lo, l1, l2, whole);
+    }
+  }
+}
+
 // SE gate applied to the ASPP concat, written as the bottleneck conv's OPERAND: out limbs = x * gate[b][c] scaled by the
 // scale of max|x| (the gate is a sigmoid: |out| <= |x|, so the input's maximum bounds the output's).  No fp32 copy, no
 // max pass, no split pass (framework/model/deeplabv2.py:99-114 -> :244).
@@ -755,6 +1007,68 @@ int onda_bn_bwd_l2(const float* dout, const void* out, int64_t out_plane, const 
   hipLaunchKernelGGL(bn_bwd_apply_l2_kernel<false>, dim3(ew_grid(total8)), dim3(256), 0, st, dout, static_cast<const _Float16*>(out),
                      (size_t)out_plane, x, mean, invstd, gamma, sums, static_cast<_Float16*>(dx), (size_t)dx_plane, dx_amax, total8,
                      C, (float)inv_m0, relu, relu_mask, (size_t)split * C / 8, (float)inv_m1, BnBwdSumsArgs{}, 0);
+  return ONDA_LAUNCH_RESULT();
+}
+
+// ---- the pair (see include/onda_hip.h) ----------------------------------------------------------------------------------------
+static bool pair_side_ok(const OndaBnSide* s, bool backward) {
+  if (!s || !s->x || !s->mean || !s->invstd || !s->xhat_amax || !s->gamma) return false;
+  return backward ? s->dx && s->dx_amax : s->partials && s->beta && s->tiles >= 1;
+}
+
+int onda_bn_pair_fwd_l2(const OndaBnSide* a, const OndaBnSide* b, float eps, int relu, void* out, float* out_amax, int64_t M, int C,
+                        uint8_t* relu_mask, int64_t split, int run_group, onda_stream_t s) {
+  ONDA_REQUIRE(pair_side_ok(a, false) && pair_side_ok(b, false) && out && out_amax && M >= 1 && C >= 32 && C % 32 == 0);
+  ONDA_REQUIRE(256 % (C / 8) == 0);  // a thread keeps its channel group across the grid stride
+  ONDA_REQUIRE(split >= 0 && split < M);
+  ONDA_REQUIRE(split == 0 || (a->tile_rows > 0 && b->tile_rows > 0 && split / a->tile_rows < a->tiles && split / b->tile_rows < b->tiles));
+  if (!ONDA_ALIGNED16(a->x) || !ONDA_ALIGNED16(b->x) || !ONDA_ALIGNED16(out) || !ONDA_ALIGNED16(a->partials) || !ONDA_ALIGNED16(b->partials))
+    return ONDA_EALIGN;
+  hipStream_t st = ONDA_STREAM(s);
+  const BnFinalizeArgs fa = finalize_args(a->partials, a->tiles, C, M, eps, a->mean, a->invstd, a->running_mean, a->running_var, a->nbt,
+                                          a->momentum, a->gamma, a->beta, nullptr, relu, a->xhat_amax, out_amax, split, a->tile_rows,
+                                          run_group, a->x, C);
+  const BnFinalizeArgs fb = finalize_args(b->partials, b->tiles, C, M, eps, b->mean, b->invstd, b->running_mean, b->running_var, b->nbt,
+                                          b->momentum, b->gamma, b->beta, nullptr, relu, b->xhat_amax, out_amax, split, b->tile_rows,
+                                          run_group, b->x, C);
+  hipLaunchKernelGGL(bn_finalize_pair_l2_kernel, dim3((C + 15) / 16, split > 0 ? 2 : 1), dim3(256), 0, st, fa, fb);
+  const size_t total8 = (size_t)M * C / 8;
+  hipLaunchKernelGGL(bn_apply_pair_l2_kernel, dim3(ew_grid(total8)), dim3(256), 0, st,
+                     BnPairSide{a->x, a->mean, a->invstd, a->gamma, a->beta}, BnPairSide{b->x, b->mean, b->invstd, b->gamma, b->beta},
+                     static_cast<_Float16*>(out), out_amax, total8, C, relu, relu_mask, (size_t)split * C / 8);
+  return ONDA_LAUNCH_RESULT();
+}
+
+int64_t onda_bn_pair_bwd_l2_ws(int64_t M, int C) {
+  const ColPlan3 p = col_plan3(M, C);
+  return (int64_t)(p.chunks + 1) * 4 * C + 6 * C;  // (+1 chunk row: two row groups round up separately; sums[2][3][C])
+}
+
+int onda_bn_pair_bwd_l2(const float* dout, const uint8_t* relu_mask, const OndaBnSide* a, const OndaBnSide* b, float* ws, int64_t M,
+                        int C, int relu, int64_t split, onda_stream_t s) {
+  ONDA_REQUIRE(dout && pair_side_ok(a, true) && pair_side_ok(b, true) && ws && M >= 1 && C >= 32 && C % 32 == 0 && (!relu || relu_mask));
+  ONDA_REQUIRE(256 % (C / 8) == 0);
+  ONDA_REQUIRE(split >= 0 && split < M);
+  if (!ONDA_ALIGNED16(dout) || !ONDA_ALIGNED16(a->x) || !ONDA_ALIGNED16(b->x) || !ONDA_ALIGNED16(a->dx) || !ONDA_ALIGNED16(b->dx) ||
+      !ONDA_ALIGNED16(ws))
+    return ONDA_EALIGN;
+  const ColPlan3 p = col_plan3(M, C);
+  int chunks0, chunks;
+  bwd_chunks(p, M, split, chunks0, chunks);
+  float* sums = ws + (size_t)(p.chunks + 1) * 4 * C;
+  hipStream_t st = ONDA_STREAM(s);
+  hipLaunchKernelGGL(bn_bwd_reduce_pair_l2_kernel, dim3(p.gridx, chunks), dim3(256), 0, st, dout, a->x, b->x, a->mean, a->invstd, b->mean,
+                     b->invstd, M, C, relu, p.cx, p.rows_per_chunk, ws, relu_mask, split, chunks0);
+  const double inv_m0 = 1.0 / (double)(split > 0 ? split : M), inv_m1 = 1.0 / (double)(M - split);
+  const int groups = split > 0 ? 2 : 1;
+  hipLaunchKernelGGL(bn_bwd_sums_pair_l2_kernel, dim3((C + 15) / 16, groups), dim3(256), 0, st,
+                     BnBwdSumsPairArgs{ws, chunks, C, inv_m0, inv_m1, BnBwdSumsSide{a->gamma, a->invstd, a->xhat_amax, a->dx_amax},
+                                       BnBwdSumsSide{b->gamma, b->invstd, b->xhat_amax, b->dx_amax}, sums, chunks0, groups});
+  const size_t total8 = (size_t)M * C / 8;
+  hipLaunchKernelGGL(bn_bwd_apply_pair_l2_kernel, dim3(ew_grid(total8)), dim3(256), 0, st, dout,
+                     BnBwdPairSide{a->x, a->mean, a->invstd, a->gamma, static_cast<_Float16*>(a->dx), a->dx_amax},
+                     BnBwdPairSide{b->x, b->mean, b->invstd, b->gamma, static_cast<_Float16*>(b->dx), b->dx_amax}, sums, total8, C,
+                     (float)inv_m0, (float)inv_m1, relu, relu_mask, (size_t)split * C / 8);
   return ONDA_LAUNCH_RESULT();
 }
 

@@ -86,11 +86,8 @@ def conv_bn(conv, bn, x, relu, residual=None):
         # residual add and the backward mask read); the conv epilogue then also leaves per-channel extrema (4 stat rows)
         limbs = ops.limb_mode(conv.out_channels)
         y, stats = conv(x, want_stats=4 if limbs else True)
-        running = (bn.running_mean, bn.running_var, bn.num_batches_tracked) if bn.track_running_stats else None
-        if bn.momentum is None:
-            raise NotImplementedError("onda_amd: cumulative-average BatchNorm (momentum=None) is not on the hot path")
         fn = ops.BNTrainLimbFn if stats.shape[1] == 4 else ops.BNTrainFn
-        return fn.apply(y, stats, bn.weight, bn.bias, residual, relu, running, bn.momentum)
+        return fn.apply(y, stats, bn.weight, bn.bias, residual, relu, _running(bn), bn.momentum)
     scale, shift = bn.folded()
     with torch.no_grad():
         wp = conv._pack.get_fwd(conv.weight)
@@ -107,6 +104,35 @@ def conv_bn(conv, bn, x, relu, residual=None):
         y, _, _ = ops.conv_forward(x, wp, k, stride, dil, pad, conv.out_channels, scale=scale, shift=shift, residual=residual,
                                    relu=relu, limb_out=limb_out)
     return y
+
+
+def _running(bn):
+    """The running buffers a train-mode BatchNorm moves (None: ``track_running_stats`` off)."""
+    if bn.momentum is None:
+        raise NotImplementedError("onda_amd: cumulative-average BatchNorm (momentum=None) is not on the hot path")
+    return (bn.running_mean, bn.running_var, bn.num_batches_tracked) if bn.track_running_stats else None
+
+
+def pair_route(conv_a, bn_a, conv_b, bn_b):
+    """Do ``relu(bn_a(conv_a(.)) + bn_b(conv_b(.)))`` run as ONE BatchNorm pass each way (ops.BNPairLimbFn)?  Both BatchNorms
+    in train mode on the limb path -- the shortcut blocks ``layerN.0`` of the BatchNorm models under the student and the EMA
+    teacher.  GroupNorm shortcuts, eval mode, the exact-fp32 conv mode and ``ONDA_BN_PAIR=0`` keep the two conv_bn calls."""
+    return (ops.BN_PAIR and all(isinstance(bn, HipBatchNorm2d) and bn.training for bn in (bn_a, bn_b))
+            and conv_a.out_channels == conv_b.out_channels and ops.limb_mode(conv_a.out_channels))
+
+
+def conv_bn_pair(conv_a, bn_a, x_a, conv_b, bn_b, x_b, relu):
+    """``conv_bn(conv_a, bn_a, x_a, relu, residual=conv_bn(conv_b, bn_b, x_b, False))`` where pair_route() holds: the same two
+    convolutions, then both BatchNorms, their add and the ReLU in one pass over the two conv outputs."""
+    y_b, stats_b = conv_b(x_b, want_stats=4)
+    y_a, stats_a = conv_a(x_a, want_stats=4)
+    if ops.bn_pair_ok(y_a, stats_a, y_b, stats_b):
+        return ops.BNPairLimbFn.apply(y_a, stats_a, bn_a.weight, bn_a.bias, _running(bn_a), bn_a.momentum,
+                                      y_b, stats_b, bn_b.weight, bn_b.bias, _running(bn_b), bn_b.momentum, relu)
+    # (a conv that did not run on the pre-split kernels, or a strided output: the two functions on the same conv outputs)
+    fns = [ops.BNTrainLimbFn if s.shape[1] == 4 else ops.BNTrainFn for s in (stats_a, stats_b)]
+    residual = fns[1].apply(y_b, stats_b, bn_b.weight, bn_b.bias, None, False, _running(bn_b), bn_b.momentum)
+    return fns[0].apply(y_a, stats_a, bn_a.weight, bn_a.bias, residual, relu, _running(bn_a), bn_a.momentum)
 
 
 class Bottleneck(nn.Module):
@@ -138,6 +164,8 @@ class Bottleneck(nn.Module):
         y = conv_bn(self.conv1, self.bn1, x, True)
         y = conv_bn(self.conv2, self.bn2, y, True)
         if self.downsample is not None:
+            if pair_route(self.conv3, self.bn3, self.downsample[0], self.downsample[1]):
+                return conv_bn_pair(self.conv3, self.bn3, y, self.downsample[0], self.downsample[1], x, True)
             residual = conv_bn(self.downsample[0], self.downsample[1], x, False)
         else:
             residual = x

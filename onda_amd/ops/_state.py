@@ -61,6 +61,11 @@ SHARE_GRADS = True  # tests turn this off to compare with autograd's own accumul
 # tools/ab_flag.py onda_amd.ops FUSE_BN_FINALIZE True -- ... to measure it again.
 FUSE_BN_FINALIZE = os.environ.get("ONDA_FUSE_BN", "0") == "1"
 
+# The first block of a ResNet layer adds two train-mode BatchNorms (conv3's and the shortcut conv's): one pass each way over
+# both (ops.BNPairLimbFn, csrc/norm_l2.hip) instead of a BNTrainLimbFn each.  ONDA_BN_PAIR=0: the two functions, for A/B and
+# for the tests that compare the routes.
+BN_PAIR = os.environ.get("ONDA_BN_PAIR", "1") != "0"
+
 # GroupNorm on a backbone convolution (ops.GNSiteFn): statistics from the conv epilogue's tile partials where no tile lies
 # across two images, instead of a reduction pass over the conv output.  tools/gn_timing.py measures both routes.
 GN_FUSED_STATS = os.environ.get("ONDA_GN_FUSED_STATS", "1") == "1"

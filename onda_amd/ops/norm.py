@@ -1,5 +1,5 @@
-"""BatchNorm (fp32 and limb-row outputs, one or two row groups), folded eval BatchNorm, max-pool, and the ASPP head's GroupNorm +
-concat and SE gate."""
+"""BatchNorm (fp32 and limb-row outputs, one or two row groups; the pair of a shortcut block in one pass), folded eval BatchNorm,
+max-pool, and the ASPP head's GroupNorm + concat and SE gate."""
 import ctypes
 import os
 from ctypes import byref
@@ -7,7 +7,7 @@ from ctypes import byref
 import torch
 
 from .. import _lib
-from .._lib import OndaConv, OndaLimbOut, call, query
+from .._lib import OndaBnSide, OndaConv, OndaLimbOut, call, query
 from . import _state
 from ._state import BN_EPS, GN_EPS, GN_GROUPS, HEAD_PAD, STEM_K
 from .core import _group_split, _p, _stream, as_nhwc, nhwc_ld
@@ -177,6 +177,71 @@ class BNTrainLimbFn(torch.autograd.Function):
         if need_res:
             dres = _sink_give(ctx.res_sink, dres, ctx.relu)
         return dx, None, None, None, dres, None, None, None
+
+
+def bn_pair_ok(y_a, stats_a, y_b, stats_b):
+    """May BNPairLimbFn take these two conv outputs?  Both on the limb path (four stat rows), dense [B,H,W,C] of one shape."""
+    return (stats_a is not None and stats_b is not None and stats_a.dim() == 3 and stats_b.dim() == 3
+            and stats_a.shape[1] == 4 and stats_b.shape[1] == 4 and y_a.dim() == 4 and y_a.shape == y_b.shape
+            and y_a.is_contiguous() and y_b.is_contiguous() and 256 % max(y_a.shape[3] // 8, 1) == 0)
+
+
+def _bn_side(y, stats, tile_rows, mean, invstd, xhat_amax, running, momentum, gamma, beta=None, dx=None, dx_amax=None):
+    rm, rv, nbt = running if running is not None else (None, None, None)
+    return OndaBnSide(_p(y), _p(stats), stats.shape[0] if stats is not None else 0, tile_rows, _p(mean), _p(invstd), _p(xhat_amax),
+                      _p(rm), _p(rv), _p(nbt), float(momentum), _p(gamma), _p(beta), _p(dx), _p(dx_amax))
+
+
+class BNPairLimbFn(torch.autograd.Function):
+    """out = [relu](BN_a(y_a) + BN_b(y_b)), both train-mode with frozen affine parameters, as limb rows only: what
+    ``BNTrainLimbFn(y_a, ..., residual=BNTrainLimbFn(y_b, ...))`` returns, without the shortcut's limb rows in between and,
+    backward, without the fp32 copy of the masked gradient.  The shortcut term is added in fp32 instead of from two f16 limbs.
+    Row groups and running statistics as BNTrainLimbFn has them, for both sides.  Backward returns the two conv-output
+    gradients as limb-only tensors; there is no residual to hand a gradient to."""
+
+    @staticmethod
+    def forward(ctx, y_a, stats_a, gamma_a, beta_a, running_a, momentum_a, y_b, stats_b, gamma_b, beta_b, running_b, momentum_b, relu):
+        B, H, W, C = y_a.shape
+        M = B * H * W
+        dev = y_a.device
+        if not bn_pair_ok(y_a, stats_a, y_b, stats_b):
+            raise RuntimeError("onda_amd: a BatchNorm pair needs two dense [B,H,W,C] conv outputs of one shape with four stat rows")
+        split = _group_split(B, H, W)
+        stat = [torch.empty((2 if split else 1) * C, device=dev, dtype=torch.float32) for _ in range(6)]
+        out_amax = amax_slot(dev)
+        rows = [_stat_tile_rows(s) if split else getattr(s, "_onda_tile_rows", 0) for s in (stats_a, stats_b)]
+        planes = torch.empty(2, M, C, device=dev, dtype=torch.float16)
+        mask = torch.empty(M * C // 8, device=dev, dtype=torch.uint8) if relu and any(ctx.needs_input_grad) else None
+        sa = _bn_side(y_a, stats_a, rows[0], stat[0], stat[1], stat[2], running_a, momentum_a, gamma_a, beta_a)
+        sb = _bn_side(y_b, stats_b, rows[1], stat[3], stat[4], stat[5], running_b, momentum_b, gamma_b, beta_b)
+        call("onda_bn_pair_fwd_l2", byref(sa), byref(sb), BN_EPS, int(relu), _p(planes), _p(out_amax), M, C, _p(mask), split, 1, _stream())
+        for running in (running_a, running_b):
+            if running is not None:
+                for t in running:
+                    torch.autograd.graph.increment_version(t)
+        ctx.split, ctx.relu, ctx.relu_mask = split, relu, mask
+        ctx.save_for_backward(y_a, y_b, gamma_a, gamma_b, *stat)
+        return limb_only((B, H, W, C), dev, Limbs(planes, out_amax, C, M * C))
+
+    @staticmethod
+    def backward(ctx, dout):
+        y_a, y_b, gamma_a, gamma_b, *stat = ctx.saved_tensors
+        B, H, W, C = y_a.shape
+        M = B * H * W
+        dev = y_a.device
+        if is_limb_only(dout):
+            raise RuntimeError("onda_amd: the gradient of a BatchNorm output must be an fp32 tensor")
+        if ctx.relu and ctx.relu_mask is None:
+            raise RuntimeError("onda_amd: a BatchNorm pair that ran without gradients has no ReLU mask to run backward with")
+        dout = dout.contiguous()
+        ws = torch.empty(query("onda_bn_pair_bwd_l2_ws", M, C), device=dev, dtype=torch.float32)
+        dx = [torch.empty(2, M, C, device=dev, dtype=torch.float16) for _ in range(2)]
+        amax = [amax_slot(dev) for _ in range(2)]
+        sa = _bn_side(y_a, None, 0, stat[0], stat[1], stat[2], None, 0.0, gamma_a, None, dx[0], amax[0])
+        sb = _bn_side(y_b, None, 0, stat[3], stat[4], stat[5], None, 0.0, gamma_b, None, dx[1], amax[1])
+        call("onda_bn_pair_bwd_l2", _p(dout), _p(ctx.relu_mask), byref(sa), byref(sb), _p(ws), M, C, int(ctx.relu), ctx.split, _stream())
+        da, db = (limb_only((B, H, W, C), dev, Limbs(dx[i], amax[i], C, M * C)) for i in range(2))
+        return da, None, None, None, None, None, db, None, None, None, None, None, None
 
 
 def fold_bounds(weight, scale, shift):
