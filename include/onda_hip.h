@@ -199,6 +199,27 @@ double onda_conv_wgrad_l2_live_fraction(const OndaConv* c, int splitk);
 int onda_conv2d_fwd_l2(const void* xl, int64_t xplane, const float* xamax, const void* w2, const float* wamax, float* y,
                        const float* scale, const float* shift, const float* residual, float* stats, int stats_rows, float* ws,
                        float* yamax, const OndaConv* c, onda_stream_t s);
+/* ---- a convolution whose taps come from a TABLE of (dh, dw) offsets: any sum of stride-1 convolutions of one input on one
+ * output grid as ONE accumulation (deeplabv2.py:71-95, ClassifierModule: four dilated 3 x 3 convolutions summed = 36 taps),
+ *   y[m, n] = sum_t sum_c x[pixel(m) + (dh_t, dw_t), c] * w[n, t*Cin + c]  (+ shift[n]) (+ residual[m, n]),
+ * on the tiles, the stream-K schedule and the epilogue of onda_conv2d_fwd_l2 (same operand formats; yamax as there).  The output
+ * grid is the input grid (c->Ho == c->Hi, c->Wo == c->Wi, stride 1); a tap that falls outside its image reads zeros, tested
+ * per image.  `taps`: a HOST array of ntaps (dh, dw) pairs, 1 <= ntaps <= 64, read during the call and handed to the kernel by
+ * value -- no device table, no synchronisation.  c->kh / kw / dil / pad are not read.  Whole tiles skip the taps that are dead
+ * for every one of their rows, as the filter-grid kernel does.  The data gradient is the same entry point: dy (channels padded
+ * to a multiple of 32) as xl, the NEGATED offsets, w2 packed [Cin rows][t*Cout_pad + n]; residual == y adds in place.
+ * onda_pack_sum_h2 writes both arrangements for nw <= 8 OIHW weights of one shape side by side along K (tap t = weight
+ * t / taps, filter tap t % taps) under ONE scale: max|w| over all of them into `amax` (zeroed), fwd[rows_pad][nw*taps*Cin] and,
+ * unless NULL, dgrad[Cin][nw*taps*Cout_pad] limb rows, rows / columns from Cout on zero; two launches.  w_oihw: a host array
+ * of nw device pointers.
+ * ONDA_EINVAL, before anything is launched: Cin % 32 != 0, ntaps outside 1..64, stride != 1 or another output grid, an offset
+ * or an image side of 2^14 or more, stats or lo non-NULL (no statistics, no limb-row output), c->run_if non-NULL, c->relu.
+ * ONDA_EALIGN: an operand, y, shift or residual not 16-byte aligned, ldy or ldr not a multiple of 4. */
+int onda_conv2d_taps_fwd_l2(const void* xl, const float* xamax, const void* w2, const float* wamax, float* y, const float* shift,
+                            const float* residual, float* stats, const OndaLimbOut* lo, float* ws, float* yamax, const OndaConv* c,
+                            const int32_t* taps, int ntaps, onda_stream_t s);
+int onda_pack_sum_h2(const float* const* w_oihw, int nw, void* fwd, void* dgrad, int Cout, int Cin, int taps, int rows_pad,
+                     int Cout_pad, float* amax, onda_stream_t s);
 
 /* ---- BatchNorm whose OUTPUT is a conv operand, written as limb planes (csrc/norm_l2.hip); same arithmetic and
  * reference call sites as onda_bn_finalize / onda_bn_apply / onda_bn_bwd (deeplabv2.py:53-68).

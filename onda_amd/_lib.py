@@ -97,6 +97,8 @@ SIGNATURES = {
     "onda_conv2d_wgrad_l2_table": (I, [POINTER(OndaConv), P, P]),
     "onda_conv2d_wgrad_l2": (I, [P, L, P, P, L, P, P, I, I, POINTER(OndaConv), P]),
     "onda_conv2d_fwd_l2": (I, [P, L, P, P, P, P, P, P, P, P, I, P, P, POINTER(OndaConv), P]),
+    "onda_conv2d_taps_fwd_l2": (I, [P, P, P, P, P, P, P, P, P, P, P, POINTER(OndaConv), POINTER(c_int), I, P]),
+    "onda_pack_sum_h2": (I, [POINTER(c_void_p), I, P, P, I, I, I, I, I, P, P]),
     "onda_bn_finalize_l2": (I, [P, I, I, L, F, P, P, P, P, P, F, P, P, P, I, P, P, L, I, I, P, I, P]),
     "onda_bn_apply_l2": (I, [P, P, P, P, P, P, L, P, P, L, P, L, I, I, P, L, P]),
     "onda_bn_bwd_l2_ws": (L, [L, I]),

@@ -51,6 +51,60 @@ __global__ void pack_h2_kernel(const float* __restrict__ w, _Float16* __restrict
   dst[o + LIMB2_OFS] = limb2(v, a);
 }
 
+// ---- the weights of a SUM of convolutions of one input, side by side along K, under ONE scale (onda_conv2d_taps_fwd_l2) -------
+// nw OIHW tensors of one shape [Cout][Cin][taps]; tap t of the table = weight t / taps, filter tap t % taps.
+//   forward rows        fwd[rows_pad][T * Cin / 32][2][32]:       row n, k = t * Cin + c        (rows Cout.. are zero)
+//   data-gradient rows  dgrad[Cin][T * Cout_pad / 32][2][32]:     row c, k = t * Cout_pad + n   (columns Cout.. of a tap are zero)
+// with T = nw * taps.  The data-gradient taps keep their order (no flip): the caller hands the kernel the NEGATED offsets.
+constexpr int SUM_MAX = 8;
+struct SumWeights {
+  const float* w[SUM_MAX];
+};
+// (selects, not an indexed read: an argument block indexed per thread is copied to scratch first)
+__device__ __forceinline__ const float* sum_weight(const SumWeights& ws, int i) {
+  const float* p = ws.w[0];
+#pragma unroll
+  for (int j = 1; j < SUM_MAX; ++j) p = i == j ? ws.w[j] : p;
+  return p;
+}
+__global__ __launch_bounds__(256) void absmax_sum_kernel(const SumWeights ws, long long n, float* __restrict__ amax) {
+  const float* w = sum_weight(ws, blockIdx.y);
+  float m = 0.f;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
+  __shared__ float red[4];
+  tile_amax_publish(amax, m, red);
+}
+__global__ __launch_bounds__(256) void pack_sum_h2_kernel(const SumWeights ws, _Float16* __restrict__ fwd, _Float16* __restrict__ dg,
+                                                          int nw, int Cout, int Cin, int taps, int rows_pad, int Cout_pad,
+                                                          const float* __restrict__ amax) {
+  const int T = nw * taps, K = T * Cin, Kd = T * Cout_pad;
+  const size_t nf = (size_t)rows_pad * K, nd = dg != nullptr ? (size_t)Cin * Kd : 0;
+  const float s = scale_of(amax).s;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < nf + nd; e += (size_t)gridDim.x * 256) {
+    float v = 0.f;
+    size_t o;
+    _Float16* dst;
+    if (e < nf) {
+      const int k = (int)(e % K), n = (int)(e / K);
+      const int t = k / Cin, cc = k - t * Cin, i = t / taps, tap = t - i * taps;
+      if (n < Cout) v = sum_weight(ws, i)[((size_t)n * Cin + cc) * taps + tap];
+      o = limb_at((size_t)n, k, K);
+      dst = fwd;
+    } else {
+      const size_t ed = e - nf;
+      const int k = (int)(ed % Kd), cc = (int)(ed / Kd);
+      const int t = k / Cout_pad, n = k - t * Cout_pad, i = t / taps, tap = t - i * taps;
+      if (n < Cout) v = sum_weight(ws, i)[((size_t)n * Cin + cc) * taps + tap];
+      o = limb_at((size_t)cc, k, Kd);
+      dst = dg;
+    }
+    v *= s;
+    const _Float16 a = limb1(v);
+    dst[o] = a;
+    dst[o + LIMB2_OFS] = limb2(v, a);
+  }
+}
+
 // ---- all conv weights of a model in two launches --------------------------------------------------
 // The student's weights change every step (SGD) and so do the teacher's (EMA): ~100 weight tensors to re-scale and
 // re-split, forward and data-gradient form.  One absmax + one pack launch per tensor cost 3 ms of launch overhead per
@@ -189,6 +243,26 @@ int onda_pack_weight_h2(const float* w_oihw, void* dst, int Cout, int Cin, int t
   const size_t plane = (size_t)rows_pad * Kp;
   hipLaunchKernelGGL(pack_h2_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, ONDA_STREAM(s), w_oihw,
                      static_cast<_Float16*>(dst), Cout, Cin, taps, rows_pad, Kp, dgrad, Cout_pad, amax);
+  return ONDA_LAUNCH_RESULT();
+}
+
+int onda_pack_sum_h2(const float* const* w_oihw, int nw, void* fwd, void* dgrad, int Cout, int Cin, int taps, int rows_pad,
+                     int Cout_pad, float* amax, onda_stream_t s) {
+  ONDA_REQUIRE(w_oihw && fwd && amax && nw >= 1 && nw <= SUM_MAX && Cout > 0 && Cin > 0 && Cin % 32 == 0 && taps > 0);
+  ONDA_REQUIRE(rows_pad >= Cout && Cout_pad >= Cout && (dgrad == nullptr || Cout_pad % 32 == 0));
+  const long long per = (long long)Cout * Cin * taps;
+  const long long total = (long long)nw * taps * ((long long)rows_pad * Cin + (dgrad ? (long long)Cin * Cout_pad : 0));
+  ONDA_REQUIRE(total * 4 < (1ll << 31));
+  SumWeights ws;
+  for (int i = 0; i < SUM_MAX; ++i) {
+    ws.w[i] = w_oihw[i < nw ? i : 0];
+    ONDA_REQUIRE(ws.w[i] != nullptr);
+  }
+  const int ab = (int)(per / 256 / 8 + 1 > 256 ? 256 : per / 256 / 8 + 1);
+  hipLaunchKernelGGL(absmax_sum_kernel, dim3(ab, nw), dim3(256), 0, ONDA_STREAM(s), ws, per, amax);
+  const int pb = (int)(total / 256 / 4 + 1 > 4096 ? 4096 : total / 256 / 4 + 1);
+  hipLaunchKernelGGL(pack_sum_h2_kernel, dim3(pb), dim3(256), 0, ONDA_STREAM(s), ws, static_cast<_Float16*>(fwd),
+                     static_cast<_Float16*>(dgrad), nw, Cout, Cin, taps, rows_pad, Cout_pad, amax);
   return ONDA_LAUNCH_RESULT();
 }
 

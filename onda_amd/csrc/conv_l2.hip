@@ -568,8 +568,47 @@ __device__ __forceinline__ void tap_offsets(unsigned (&aofs)[APW], const RowPos 
 #pragma unroll
   for (int d = 0; d < APW; ++d) aofs[d] = row_tap_ofs(rp[d], rr, ss, c, cq[d & 1]);
 }
-template <int WM, int WN, int STAGES, int OCC, bool SK, int DBG = 0>
-__global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2_kernel(const ConvK a, unsigned xplane, unsigned wplane, unsigned x_bytes,
+// ---- where a K-step's taps read: the (kh, kw, dil, pad) grid of ONE convolution (ConvK), or a TABLE of (dh, dw) offsets -- any
+// sum of stride-1 convolutions of one input on one output grid (the four dilated branches of the DeepLabV2 'normal' head: 36
+// taps) as one accumulation.  The table travels in the kernel's argument block; the host sets stride 1, dil 1, pad 0 in `c`, so
+// that row_pos is the output pixel itself and row_tap_ofs adds the tap's offset as it stands.  Everything that asks "where
+// does tap tp read" goes through these overloads on the argument block: the grid forms are the lines the kernel always had.
+constexpr int TAPS_MAX = 64;
+struct TapTable {
+  int d[TAPS_MAX];  // (dh & 0xFFFF) | dw << 16
+};
+struct ConvKTaps : ConvK {
+  TapTable tab;
+};
+__device__ __forceinline__ int tab_dh(const TapTable& t, int tp) { return (int)(short)(t.d[tp] & 0xFFFF); }
+__device__ __forceinline__ int tab_dw(const TapTable& t, int tp) { return t.d[tp] >> 16; }
+template <int APW>
+__device__ __forceinline__ void tap_offsets(unsigned (&aofs)[APW], const RowPos (&rp)[APW], int tp, const ConvK& a, const unsigned (&cq)[2]) {
+  tap_offsets(aofs, rp, tp, a.c, cq);
+}
+template <int APW>
+__device__ __forceinline__ void tap_offsets(unsigned (&aofs)[APW], const RowPos (&rp)[APW], int tp, const ConvKTaps& a, const unsigned (&cq)[2]) {
+  const int dh = tab_dh(a.tab, tp), dw = tab_dw(a.tab, tp);
+#pragma unroll
+  for (int d = 0; d < APW; ++d) aofs[d] = row_tap_ofs(rp[d], dh, dw, a.c, cq[d & 1]);
+}
+// row offset of tap tp (the dead-tap test of a tile), and: does the tap's COLUMN offset alone put every pixel outside the image?
+__device__ __forceinline__ int tap_dh(const ConvK& a, int tp) { return (tp / a.c.kw) * a.c.dil - a.c.pad; }
+__device__ __forceinline__ int tap_dh(const ConvKTaps& a, int tp) { return tab_dh(a.tab, tp); }
+__device__ __forceinline__ bool tap_cols_dead(const ConvK&, int) { return false; }
+__device__ __forceinline__ bool tap_cols_dead(const ConvKTaps& a, int tp) {
+  const int dw = tab_dw(a.tab, tp);
+  return dw >= a.c.Wi || -dw >= a.c.Wi;
+}
+// one bit per tap: 32 for a filter grid (at most 7 x 7 = 49 taps never reach this kernel: the stem is a flat 1 x 1), 64 for a table
+template <class KA> struct LiveTaps { using T = unsigned; };
+template <> struct LiveTaps<ConvKTaps> { using T = unsigned long long; };
+__device__ __forceinline__ int live_count(unsigned live, int taps) { return __builtin_popcount(live & ((1u << taps) - 1u)); }
+__device__ __forceinline__ int live_count(unsigned long long live, int taps) {
+  return __builtin_popcountll(taps >= 64 ? live : live & ((1ull << taps) - 1ull));
+}
+template <int WM, int WN, int STAGES, int OCC, bool SK, int DBG = 0, class KA = ConvK>
+__global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2_kernel(const KA a, unsigned xplane, unsigned wplane, unsigned x_bytes,
                                                                    unsigned w_bytes, const float* __restrict__ xamax,
                                                                    const float* __restrict__ wamax) {
   if (a.c.run_if != nullptr && *a.c.run_if == 0) return;  // predicated launch (onda_switch_step decided on the device)
@@ -633,22 +672,25 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2_kernel(const ConvK 
     // Filter taps whose input rows all lie outside the image for EVERY output row of this tile (whole image rows of a
     // dilated tap: a quarter of the K-steps of the dilation-24 ASPP branch) contribute exact zeros: a whole tile skips
     // them -- no DMA, no MFMA.  (Stream-K pieces keep the full K range their unit arithmetic is written in.)
-    unsigned live = 0xFFFFFFFFu;
+    using Live = typename LiveTaps<KA>::T;
+    Live live = ~Live(0);
     if (dp && a.taps > 1 && a.skip_dead_taps) {
       live = 0;
       const int m_last = min(a.M, m0 + BM) - 1;
       const int r0 = m0 / c.Wo, r1 = m_last / c.Wo;  // global output rows (b*Ho + ho) the tile touches
       const int ho0 = r0 % c.Ho;
       for (int tp = 0; tp < a.taps; ++tp) {
-        const int dh = (tp / c.kw) * c.dil - c.pad;
+        const int dh = tap_dh(a, tp);
         bool alive = false;
         for (int r = r0, ho = ho0; r <= r1; ++r) {
           alive |= (unsigned)(ho * c.stride + dh) < (unsigned)c.Hi;
           if (++ho == c.Ho) ho = 0;
         }
-        live |= (alive ? 1u : 0u) << tp;
+        if (tap_cols_dead(a, tp)) alive = false;
+        live |= (Live)(alive ? 1u : 0u) << tp;
       }
-      if (live == 0) live = 1;  // (cannot happen for a tile with a valid row and pad < kernel reach; keeps the loop non-empty)
+      if (live == 0) live = 1;  // (a grid: cannot happen for a tile with a valid row and pad < kernel reach; a table whose taps all
+                                //  miss the image: one K-step of zeros.  Keeps the loop non-empty)
     }
     auto next_live_tap = [&](int tp) {
       while (tp < a.taps && !((live >> tp) & 1u)) ++tp;
@@ -657,7 +699,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2_kernel(const ConvK 
     unsigned aofs[APW];
     int tap_i = dp ? next_live_tap(0) : k_begin / a.kcper;
     int c0_i = dp ? 0 : (k_begin - tap_i * a.kcper) * BK;  // the K-step the next issue() fetches
-    auto set_tap = [&](int tp) { tap_offsets(aofs, rp, tp, c, cq); };
+    auto set_tap = [&](int tp) { tap_offsets(aofs, rp, tp, a, cq); };
     auto issue = [&](int stage_off) {
 #if defined(__HIP_DEVICE_COMPILE__)
       const int sa = c0_i * 4;                       // the row's 128-byte block of channels c0 .. c0 + 31
@@ -689,7 +731,7 @@ __global__ __launch_bounds__(WM * WN * 64, OCC) void conv_l2_kernel(const ConvK 
     __syncthreads();  // the previous tile's readers (fragments, epilogue scratch) are done with every LDS region
     set_tap(tap_i);
     int st_issue = 0, st_read = 0;  // byte offsets of the ring stages
-    const int nsteps = dp && a.taps > 1 && a.skip_dead_taps ? __builtin_popcount(live & ((1u << a.taps) - 1u)) * a.kcper : k_end - k_begin;
+    const int nsteps = dp && a.taps > 1 && a.skip_dead_taps ? live_count(live, a.taps) * a.kcper : k_end - k_begin;
     issue(st_issue);
     st_issue += STAGE;
     if (AHEAD == 2 && nsteps > 1) {
@@ -2108,7 +2150,8 @@ int l2_variant_mc(long long M, int Cout, const L2Overrides& o) {
 // 72-step tiles -- 256 -> 256 3 x 3 -- 130 us on the stream kernel against 120.5, 144-step tiles 391 against 363.)
 constexpr int L2X_MAX_KSTEPS = 32;
 
-struct L2Epilogue { bool plain; bool dense_out; long long y_total; };  // what l2_fwd_impl knows and the queries do not
+// what l2_fwd_impl knows and the queries do not (tile_only: a tap-table launch -- conv_l2_kernel is the kernel that reads the table)
+struct L2Epilogue { bool plain; bool dense_out; long long y_total; bool tile_only = false; };
 
 /* How onda_conv2d_fwd_l2 / _limbs run an (M, Cout, K) problem, decided HERE and nowhere else: l2_fwd_impl launches what the
  * plan says, the public queries read it.  kernel: the tile variant (0: 256 x 128, 1: 128 x 128, 2: 256 x 64 = conv_l2_kernel<4,2> /
@@ -2179,8 +2222,9 @@ L2Plan l2_plan(long long M, int Cout, int taps, int Cin, bool have_ws, long long
   // conv_l2a_kernel takes the plain epilogue (with or without statistics) and a dense output.  Everything else -- scale /
   // shift / residual / ReLU / max|y|, limb-row outputs, scattered outputs -- stays on the 128 x 128 tile kernel.  The stream
   // kernel addresses the output as one buffer: dense rows relative to the tile (any size), scattered ones below 2 GiB.
-  if (stationary && (!epi || (epi->plain && epi->dense_out))) q.kernel = 4;
-  else if (q.variant == 0 && KT <= L2X_MAX_KSTEPS && (!epi || epi->dense_out || epi->y_total < 0x7FFFF000ll)) q.kernel = 3;
+  const bool tile_only = epi && epi->tile_only;
+  if (stationary && !tile_only && (!epi || (epi->plain && epi->dense_out))) q.kernel = 4;
+  else if (q.variant == 0 && KT <= L2X_MAX_KSTEPS && !tile_only && (!epi || epi->dense_out || epi->y_total < 0x7FFFF000ll)) q.kernel = 3;
   else q.kernel = q.variant;
   q.tiles_dp = q.kernel == 3 && !q.balanced ? tiles : tiles - q.rem;  // (the stream kernel is persistent either way: whole tiles only)
   if (q.kernel == 4) q.grid = tiles < cus ? tiles : cus;  // one workgroup of 8 waves per CU
@@ -2261,7 +2305,9 @@ double onda_conv_wgrad_l2_live_fraction(const OndaConv* c, int splitk) {
 
 static int l2_fwd_impl(const void* xl, int64_t xplane, const float* xamax, const void* w2, const float* wamax, float* y,
                        const float* scale, const float* shift, const float* residual, float* stats, int stats_rows, float* ws,
-                       float* yamax, const OndaConv* c, onda_stream_t s, const OndaLimbOut* lo) {
+                       float* yamax, const OndaConv* c, onda_stream_t s, const OndaLimbOut* lo, const TapTable* tab = nullptr) {
+  // (tab: onda_conv2d_taps_fwd_l2 -- `c` is then its own copy of the caller's geometry with kh * kw = the table's taps, stride 1,
+  //  dil 1, pad 0: the checks and the operand sizes below are those of that 1 x ntaps filter)
   ONDA_REQUIRE(xl && xamax && w2 && wamax && (y || lo) && c && ws && (stats_rows == 2 || stats_rows == 4));
   if (lo != nullptr) {  // limb-plane output: dense [M][ldy] planes, no statistics, residual (if any) as limb planes
     ONDA_REQUIRE(lo->out && lo->out_bound && lo->kb && lo->xtrue && !stats && !residual);
@@ -2321,7 +2367,7 @@ static int l2_fwd_impl(const void* xl, int64_t xplane, const float* xamax, const
   const bool dense_out = c->out_os == 1 && c->Hf == c->Ho && c->Wf == c->Wo;
   const long long y_rows = (long long)c->B * (dense_out ? (long long)c->Ho * c->Wo : (long long)c->Hf * c->Wf);
   const long long y_total = ((y_rows - 1) * c->ldy + c->Cout) * 4;
-  const L2Epilogue epi = {lo == nullptr && !scale && !shift && !residual && !c->relu && !yamax, dense_out, y_total};
+  const L2Epilogue epi = {lo == nullptr && !scale && !shift && !residual && !c->relu && !yamax, dense_out, y_total, tab != nullptr};
   const L2Plan q = l2_plan(M, c->Cout, k.taps, c->Cin, true, stats ? (long long)c->stat_split : 0, c->plain_schedule != 0, &epi);
   ONDA_REQUIRE(q.variant >= 0 && q.variant <= 2);  // (an ONDA_L2_VARIANT that names no tile)
   k.tilesM = q.tilesM;
@@ -2346,6 +2392,30 @@ static int l2_fwd_impl(const void* xl, int64_t xplane, const float* xamax, const
   } while (0)
 #define L2A_LAUNCH(KB_, NST_, A2L_) \
   hipLaunchKernelGGL((conv_l2a_kernel<KB_, NST_, A2L_, 0>), dim3(q.grid), dim3(512), 0, st, k, w_bytes, (unsigned)y_total, xamax, wamax)
+  if (tab != nullptr) {  // the tile kernels with the tap table in their argument block; the remainder's fix-up never asks where a tap reads
+    ConvKTaps kt;
+    static_cast<ConvK&>(kt) = k;
+    kt.tab = *tab;
+#define L2_LAUNCH_TAPS(WM_, WN_, ST_, OCC_)                                                                                  \
+  do {                                                                                                                       \
+    if (q.balanced) {                                                                                                        \
+      hipLaunchKernelGGL((conv_l2_kernel<WM_, WN_, ST_, OCC_, true, 0, ConvKTaps>), dim3(q.grid), dim3(WM_ * WN_ * 64), 0, st, kt, xpl, \
+                         wpl, x_bytes, w_bytes, xamax, wamax);                                                               \
+      L2_FIXUP(64 * WM_, 64 * WN_);                                                                                          \
+    } else {                                                                                                                 \
+      hipLaunchKernelGGL((conv_l2_kernel<WM_, WN_, ST_, OCC_, false, 0, ConvKTaps>), dim3(q.grid), dim3(WM_ * WN_ * 64), 0, st, kt, xpl, \
+                         wpl, x_bytes, w_bytes, xamax, wamax);                                                               \
+    }                                                                                                                        \
+  } while (0)
+    switch (q.kernel) {
+      case 0: L2_LAUNCH_TAPS(4, 2, 3, 2); break;
+      case 1: L2_LAUNCH_TAPS(2, 2, 2, 2); break;
+      case 2: L2_LAUNCH_TAPS(4, 1, 2, 2); break;
+      default: return ONDA_EINVAL;  // (l2_plan names a tile kernel for a tile_only launch)
+    }
+#undef L2_LAUNCH_TAPS
+    return ONDA_LAUNCH_RESULT();
+  }
   switch (q.kernel) {
     case 0:
 #ifdef ONDA_L2_ABLATIONS
@@ -2395,6 +2465,30 @@ int onda_conv2d_fwd_l2_limbs(const void* xl, int64_t xplane, const float* xamax,
                              onda_stream_t s) {
   ONDA_REQUIRE(lo != nullptr);
   return l2_fwd_impl(xl, xplane, xamax, w2, wamax, nullptr, scale, shift, nullptr, nullptr, 2, ws, nullptr, c, s, lo);
+}
+
+int onda_conv2d_taps_fwd_l2(const void* xl, const float* xamax, const void* w2, const float* wamax, float* y, const float* shift,
+                            const float* residual, float* stats, const OndaLimbOut* lo, float* ws, float* yamax, const OndaConv* c,
+                            const int32_t* taps, int ntaps, onda_stream_t s) {
+  ONDA_REQUIRE(c && taps && ntaps >= 1 && ntaps <= TAPS_MAX && y);
+  ONDA_REQUIRE(stats == nullptr && lo == nullptr && c->run_if == nullptr);
+  ONDA_REQUIRE(c->Cin > 0 && c->Cin % 32 == 0 && c->stride == 1 && c->out_os == 1 && !c->relu);
+  ONDA_REQUIRE(c->Ho == c->Hi && c->Wo == c->Wi && c->Hf == c->Ho && c->Wf == c->Wo && c->Hi > 0 && c->Wi > 0);
+  // RowPos holds a pixel's row and column in 16 bits each, the table an offset in 16 bits: both sums stay below 2^15
+  ONDA_REQUIRE(c->Hi < 16384 && c->Wi < 16384);
+  TapTable tab;
+  for (int t = 0; t < TAPS_MAX; ++t) {
+    const int dh = t < ntaps ? taps[2 * t] : 0, dw = t < ntaps ? taps[2 * t + 1] : 0;
+    ONDA_REQUIRE(dh > -16384 && dh < 16384 && dw > -16384 && dw < 16384);
+    tab.d[t] = (int)((unsigned)(dh & 0xFFFF) | ((unsigned)dw << 16));
+  }
+  OndaConv g = *c;  // what the kernels read of a tap's place comes from the table: kh / kw / dil / pad of the caller are not looked at
+  g.kh = 1;
+  g.kw = ntaps;
+  g.dil = 1;
+  g.pad = 0;
+  g.stat_split = 0;
+  return l2_fwd_impl(xl, 0, xamax, w2, wamax, y, nullptr, shift, residual, nullptr, 2, ws, yamax, &g, s, nullptr, &tab);
 }
 
 // weight-gradient tile of the pre-split kernel for a (Cout, Cin) problem: 0 = 256 output x 128 input channels (8 waves),

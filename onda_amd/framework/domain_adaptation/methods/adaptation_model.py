@@ -101,6 +101,11 @@ class _Interp(nn.Module):
 
 class da_model:
     def __init__(self, model, cfg, cfg_spec) -> None:
+        if not getattr(model, "feat", True):
+            # the 'normal' head returns bare logits; everything below indexes ["out"] / ["feat"] (the reference's adaptation
+            # methods fail with a TypeError at their first step): such a model trains through segmentation.train
+            raise NotImplementedError("onda_amd: the adaptation methods need a model with features (MODEL.CLASSIFIER: 'ProDA'); "
+                                      "a 'normal'-head model is trained and evaluated by segmentation.train / SegmentationTrainer")
         self.model, self.cfg, self.cfg_spec = model, cfg, cfg_spec
         self.device = cfg.OTHERS.DEVICE
         self.bn = batchnorm_stats(model)

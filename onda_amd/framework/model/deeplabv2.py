@@ -10,7 +10,9 @@ time, ``deepcopy`` works, and ``optim_parameters(lr)`` walks the tree exactly as
 (duplicate entries included); the construction order and init recipe (:210-241, :326-331),
 so a given torch seed produces the same initial weights.  ``norm_module`` may be the handler's GroupNorm lambda
 (``DeepLabv2-Resnet50-GN``): as in the reference it reaches the stem's ``bn1`` and the four ``layerN.0.downsample.1`` only
-(361 keys), which then run on ``ops.GNSiteFn``.
+(361 keys), which then run on ``ops.GNSiteFn``.  ``classifier="normal"`` (the default argument; any string but ``"ProDA"``) builds
+the original DeepLabV2 / ADVENT head, ``ClassifierModule`` -- ``forward`` then returns two logit tensors and ``feat`` is False --
+once ``enable_normal_classifier()`` or ``ONDA_NORMAL_HEAD=1`` has switched it on; left alone the constructor refuses it.
 
 What is different: inside ``forward`` activations are NHWC and every op is a HIP kernel;
 `feat` / `out` come back as NCHW-shaped views of pixel-major buffers (no copy), which is
@@ -285,14 +287,60 @@ class Classifier_Module2(nn.Module):
         return out
 
 
+class ClassifierModule(nn.Module):
+    """The original DeepLabV2 / ADVENT head (reference :71-95): dilated 3x3 convolutions with bias from the backbone's channels
+    straight to the classes, their outputs summed.  Same ``conv2d_list.{i}.{weight,bias}`` keys and ``normal_(0, 0.01)`` init.
+    ``forward(x)`` returns the logits ``f32[B,K,h,w]`` -- a tensor, not a dict: this head has no ``feat``.  The sum runs as
+    ``ops.SumConvFn``: one tap-table launch each way or one launch per branch (``ops.sum_conv_route``)."""
+
+    def __init__(self, inplanes, dilation_series, padding_series, num_classes):
+        super().__init__()
+        self.num_classes = num_classes
+        self.conv2d_list = nn.ModuleList()
+        for dilation, padding in zip(dilation_series, padding_series):
+            conv = HipConv2d(inplanes, num_classes, kernel_size=3, stride=1, padding=padding, dilation=dilation, bias=True)
+            conv._onda_sum_packed = True  # packed by this module's own cache, not by the model's packer
+            self.conv2d_list.append(conv)
+        for m in self.conv2d_list:
+            m.weight.data.normal_(0, 0.01)
+        self._pack = ops._SumPack(len(self.conv2d_list))
+
+    def forward(self, x):
+        ops.share_grad(x)  # layer3's output also feeds layer4: the data gradients meet in one buffer (ops.GradSink)
+        convs = list(self.conv2d_list)
+        geoms = tuple((c.kernel_size[0], c.dilation[0], c.padding[0]) for c in convs)
+        out_pad = ops.SumConvFn.apply(x, self._pack, geoms, ops.HEAD_PAD, *[c.weight for c in convs], *[c.bias for c in convs])
+        return ops.ClassSliceFn.apply(out_pad, self.num_classes)
+
+
+# MODEL.CLASSIFIER 'normal' (and any other string but 'ProDA': the reference's default branch) is an opt-in, because the
+# library's contract so far was to refuse it: enable_normal_classifier(), or ONDA_NORMAL_HEAD=1 in the environment at import.
+_normal_head = os.environ.get("ONDA_NORMAL_HEAD", "0") == "1"
+
+
+def enable_normal_classifier(on=True):
+    """Let get_deeplab_v2 build the 'normal' classifier head (ClassifierModule); ``on=False`` restores the refusal.  Returns
+    the previous setting."""
+    global _normal_head
+    old, _normal_head = _normal_head, bool(on)
+    return old
+
+
 class ResNetMulti(nn.Module):
     def __init__(self, block, layers, num_classes, multi_level, classifier_module="normal",
                  norm_module=HipBatchNorm2d, norm_grad=False):
-        if classifier_module != "ProDA":
-            raise NotImplementedError("onda_amd implements the ProDA classifier head (MODEL.CLASSIFIER: 'ProDA'), the one "
-                                      "the hybrid_switch / static_model configs use")
+        if classifier_module != "ProDA" and not _normal_head:
+            raise NotImplementedError("onda_amd builds the ProDA classifier head (MODEL.CLASSIFIER: 'ProDA'), the one the "
+                                      "hybrid_switch / static_model configs use, unless the 'normal' DeepLabV2 / ADVENT head is "
+                                      "switched on: deeplabv2.enable_normal_classifier() or ONDA_NORMAL_HEAD=1")
         self.multi_level = multi_level
-        self.feat = True
+        self.feat = classifier_module == "ProDA"
+        if classifier_module == "ProDA":
+            clf_module = Classifier_Module2
+        else:
+            if classifier_module != "normal":
+                print("Using default ADVENT CLF")
+            clf_module = ClassifierModule
         self.inplanes = 64
         super().__init__()
         self.conv1 = HipConv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
@@ -309,8 +357,8 @@ class ResNetMulti(nn.Module):
         self.layer4 = self._make_layer(block, 512, layers[3], stride=1, dilation=4, norm_module=norm_module,
                                        norm_grad=norm_grad)
         if self.multi_level:
-            self.layer5 = Classifier_Module2(1024, [6, 12, 18, 24], [6, 12, 18, 24], num_classes)
-        self.layer6 = Classifier_Module2(2048, [6, 12, 18, 24], [6, 12, 18, 24], num_classes)
+            self.layer5 = clf_module(1024, [6, 12, 18, 24], [6, 12, 18, 24], num_classes)
+        self.layer6 = clf_module(2048, [6, 12, 18, 24], [6, 12, 18, 24], num_classes)
         for m in self.modules():  # reference :326-331 (this also overrides the head's own init)
             if isinstance(m, nn.Conv2d):
                 m.weight.data.normal_(0, 0.01)
@@ -377,16 +425,22 @@ class ResNetMulti(nn.Module):
         packer = self.__dict__.get("_packer")
         if packer is None:
             plain = [m for name, m in self.named_modules() if isinstance(m, HipConv2d) and m is not self.conv1
-                     and not name.endswith("head.1") and (self.multi_level or not name.startswith("layer5."))]
+                     and not name.endswith("head.1") and (self.multi_level or not name.startswith("layer5."))
+                     and not getattr(m, "_onda_sum_packed", False)]
             packer = self.__dict__["_packer"] = ops.ModelPacker(plain)
         packer.refresh(need_dgrad=torch.is_grad_enabled() and self.training)
         y = self._stem(x)
         y = self.layer1(y)
         y = self.layer2(y)
         y = self.layer3(y)
-        x1 = self.layer5(y, True) if self.multi_level else None
-        y = self.layer4(y)
-        x2 = self.layer6(y, True)
+        if self.feat:
+            x1 = self.layer5(y, True) if self.multi_level else None
+            y = self.layer4(y)
+            x2 = self.layer6(y, True)
+        else:  # the 'normal' head (reference :383-394): logits as they are, no dict
+            x1 = self.layer5(y) if self.multi_level else None
+            y = self.layer4(y)
+            x2 = self.layer6(y)
         return x1, x2
 
     # ---- parameter groups: the same nested walk as the reference (:397-439) -----------------

@@ -15,9 +15,9 @@ from . import _state, conv, core, disc, limbs, loss, norm, tables
 from ._state import BN_EPS, GN_EPS, GN_GROUPS, HEAD_PAD, STEM_K
 
 # The switches live in `_state` (CONV_MODE, H2_PATH, GRAD_READY, PROFILE, PREDICATE, ROW_GROUPS, LIMB_ONLY, SHARE_GRADS,
-# FUSE_BN_FINALIZE, GN_FUSED_STATS, BN_PAIR): `ops.CONV_MODE` reads it, `ops.CONV_MODE = "f32"` writes it -- the submodules look there at call time.
+# FUSE_BN_FINALIZE, GN_FUSED_STATS, BN_PAIR, TAP_CONV): `ops.CONV_MODE` reads it, `ops.CONV_MODE = "f32"` writes it -- the submodules look there at call time.
 _FLAGS = ("CONV_MODE", "H2_PATH", "GRAD_READY", "PROFILE", "PREDICATE", "ROW_GROUPS", "LIMB_ONLY", "SHARE_GRADS", "FUSE_BN_FINALIZE",
-          "GN_FUSED_STATS", "BN_PAIR")
+          "GN_FUSED_STATS", "BN_PAIR", "TAP_CONV")
 
 # everything else of the submodules under the names the single module had (tests, tools, bench.py and the framework mirror use
 # `ops.<name>`, underscore names included); to replace a function that OTHER ops code calls, patch it in its submodule

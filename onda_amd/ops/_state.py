@@ -66,6 +66,12 @@ FUSE_BN_FINALIZE = os.environ.get("ONDA_FUSE_BN", "0") == "1"
 # for the tests that compare the routes.
 BN_PAIR = os.environ.get("ONDA_BN_PAIR", "1") != "0"
 
+# A sum of stride-1 convolutions of one input (ops.SumConvFn: the four dilated branches of the DeepLabV2 'normal' head) as ONE
+# tap-table launch each way (onda_conv2d_taps_fwd_l2) instead of four launches chained through the residual operand.  "f16x2"
+# only; tools/head_timing.py measures both routes, docs/experiments.md "Tap-table convolution" has the figures the default
+# rests on (forward -7 %, data gradient -25 %, packing 26 us against 126).  ONDA_TAP_CONV=0: the chained launches.
+TAP_CONV = os.environ.get("ONDA_TAP_CONV", "1") != "0"
+
 # GroupNorm on a backbone convolution (ops.GNSiteFn): statistics from the conv epilogue's tile partials where no tile lies
 # across two images, instead of a reduction pass over the conv output.  tools/gn_timing.py measures both routes.
 GN_FUSED_STATS = os.environ.get("ONDA_GN_FUSED_STATS", "1") == "1"

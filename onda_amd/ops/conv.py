@@ -486,6 +486,170 @@ class Conv2dFn(torch.autograd.Function):
         return dx, dw, db, None, None, None, None, None, None
 
 
+# ------------------------------------------------------------------- a sum of convolutions of one input (tap tables)
+def sum_taps(geoms, negate=False):
+    """(dh, dw) of every tap of a sum of k x k stride-1 convolutions on one grid, geoms = ((k, dil, pad), ...) with
+    2 * pad == dil * (k - 1), in the order onda_pack_sum_h2 lays the weights out along K: convolution by convolution, filter taps
+    row-major.  negate: the offsets of the data gradient (dx[q] collects dy[q - offset])."""
+    sign = -1 if negate else 1
+    return [(sign * (r * dil - pad), sign * (s * dil - pad)) for k, dil, pad in geoms for r in range(k) for s in range(k)]
+
+
+def sum_conv_route(cin, cout_pad):
+    """"taps": one tap-table launch each way; "chain": one launch of the existing kernels per convolution, chained through the
+    residual operand (the exact-fp32 mode, ONDA_TAP_CONV=0, shapes the pre-split kernels do not take, predicated passes)."""
+    taps = (_state.TAP_CONV and _state.CONV_MODE == "f16x2" and _state.H2_PATH == "dma" and cin % 32 == 0 and cout_pad % 32 == 0
+            and _state.PREDICATE is None)
+    return "taps" if taps else "chain"
+
+
+def conv_taps(x, wp, offsets, cout, out=None, shift=None, residual=None, yamax=None, kind="fwd"):
+    """One onda_conv2d_taps_fwd_l2 launch: y[B,H,W,cout] = sum_t x[pixel + offsets[t]] @ w_t.T (+ shift) (+ residual) on the grid
+    of x.  x: NHWC activation (fp32 or limb-only); wp: H2Weight rows [cout][len(offsets) * Cin] (onda_pack_sum_h2);
+    `residual` may be `out` itself: the launch then adds into it in place (GradSink)."""
+    _require_cuda(x, "conv input")
+    B, H, W, Cin = x.shape
+    if not _use_l2(wp, Cin) or _state.PREDICATE is not None:
+        raise RuntimeError("onda_amd: the tap-table conv runs on the pre-split kernels only (\"f16x2\", Cin % 32 == 0, no predicate)")
+    xl = limbs_of(x)
+    if out is None:
+        out = torch.empty(B, H, W, cout, device=x.device, dtype=torch.float32)
+    else:  # (as conv_forward: a caller's buffer is rewritten behind torch's version counter)
+        for attr in ("_onda_scale", "_onda_limbs"):
+            if getattr(out, attr, None) is not None:
+                delattr(out, attr)
+    d = _desc(B, H, W, Cin, H, W, cout, 1, 1, 1, 0, xl.ld, nhwc_ld(out), nhwc_ld(residual) if residual is not None else 0)
+    flat = [v for o in offsets for v in o]
+    table = (ctypes.c_int * len(flat))(*flat)
+    M, T = B * H * W, len(offsets)
+    _launch(_l2_name(M, cout, T, Cin), 2.0 * M * cout * T * Cin, "onda_conv2d_taps_fwd_l2", _p(xl.planes), _p(xl.amax), _p(wp.limbs),
+            _p(wp.amax), _p(out), _p(shift), _p(residual), None, None, _p(_conv_ws(x.device)), _p(yamax), byref(d), table, T, _stream(),
+            tag=(kind + "_taps", M, cout, Cin, T))
+    return out
+
+
+class _SumPack:
+    """What ops.SumConvFn keeps of its parameters: for the tap-table route the forward and the data-gradient rows of ALL weights
+    side by side along K under one scale (two launches per parameter version, onda_pack_sum_h2), for the chained route a
+    _PackCache per weight, and the sum of the biases as the padded shift vector.  Keyed on the parameters' versions, as
+    _PackCache is."""
+
+    def __init__(self, n):
+        self.each = [_PackCache() for _ in range(n)]
+        self.key = self.key_b = None
+        self.fwd = self.dgrad = self.shift = None
+
+    def get(self, weights, cout_pad, need_dgrad):
+        key = tuple(_PackCache._key(w) for w in weights) + (cout_pad,)
+        if self.key != key or (need_dgrad and self.dgrad is None):
+            if any(w.shape != weights[0].shape for w in weights):
+                raise RuntimeError("onda_amd: the convolutions of a tap-table sum share one weight shape")
+            cout, cin, kh, kw = weights[0].shape
+            ws = [w.detach().contiguous() for w in weights]
+            T = len(ws) * kh * kw
+            dev = ws[0].device
+            slot = amax_slot(dev, long_lived=True)  # max over all of them: no single weight's max|w|, so nothing is tagged
+            fwd = torch.empty(2, cout_pad, T * cin, device=dev, dtype=torch.float16)
+            dg = torch.empty(2, cin, T * cout_pad, device=dev, dtype=torch.float16) if need_dgrad else None
+            ptrs = (ctypes.c_void_p * len(ws))(*[w.data_ptr() for w in ws])
+            call("onda_pack_sum_h2", ptrs, len(ws), _p(fwd), _p(dg), cout, cin, kh * kw, cout_pad, cout_pad, _p(slot), _stream())
+            self.fwd, self.dgrad, self.key = H2Weight(fwd, slot), (H2Weight(dg, slot) if need_dgrad else None), key
+        return self
+
+    def bias_sum(self, biases, n):
+        key = tuple((b.data_ptr(), b._version) for b in biases) + (n,)
+        if self.key_b != key:
+            with torch.no_grad():
+                self.shift, self.key_b = _pad_vec(torch.stack([b.detach() for b in biases]).sum(0), n), key
+        return self.shift
+
+    def __deepcopy__(self, memo):
+        return _SumPack(len(self.each))
+
+
+class SumConvFn(torch.autograd.Function):
+    """sum_i conv_i(x) (+ sum_i bias_i) of k x k stride-1 convolutions that keep the grid -- the reference's ClassifierModule
+    (deeplabv2.py:71-95) -- as padded NHWC logits [B,H,W,cout_pad].  apply(x, cache, geoms, cout_pad, *weights, *biases) with
+    cache a _SumPack, geoms ((k, dil, pad), ...), biases all or none.  Routes: sum_conv_route().  The weight gradients are
+    one launch per convolution on either route (they share the limb rows of x and of dy); the bias gradient is one colsum."""
+
+    @staticmethod
+    def forward(ctx, x, cache, geoms, cout_pad, *params):
+        _require_cuda(x, "conv input")
+        n = len(geoms)
+        weights, biases = params[:n], params[n:]
+        if len(biases) not in (0, n) or any(2 * pad != dil * (k - 1) for k, dil, pad in geoms):
+            raise RuntimeError("onda_amd: SumConvFn takes grid-preserving stride-1 convolutions, with all biases or none")
+        cout, cin = weights[0].shape[:2]
+        co = cout_pad or cout
+        shift = cache.bias_sum(biases, co) if biases else None
+        route = sum_conv_route(cin, co)
+        if route == "taps":
+            y = conv_taps(x, cache.get(weights, co, False).fwd, sum_taps(geoms), co, shift=shift)
+        else:
+            y = None
+            for i, (w, (k, dil, pad)) in enumerate(zip(weights, geoms)):
+                wp = cache.each[i].get_fwd(w, cout_pad)
+                # pre-split kernels: the running sum is the residual AND the output (same thread, same 16 bytes: conv_dgrad)
+                out = y if (y is not None and _use_l2(wp, cin)) else None
+                y, _, _ = conv_forward(x, wp, k, 1, dil, pad, co, out=out, shift=shift if i == 0 else None, residual=y)
+        ctx.save_for_backward(x, *weights)
+        hit = getattr(x, "_onda_limbs", None)
+        ctx.xlimbs = hit[1] if hit is not None and hit[0] == x._version else None
+        ctx.params = params  # the Parameters themselves: their .grad is the accumulation target
+        ctx.sink = _sink_of(x) if ctx.needs_input_grad[0] else None
+        ctx.cache, ctx.geoms, ctx.dims, ctx.route = cache, geoms, (cout, cin, cout_pad, co), route
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        n = len(ctx.geoms)
+        if dy is None:
+            return (None,) * (4 + len(ctx.params))
+        x, *weights = ctx.saved_tensors
+        cout, cin, cout_pad, co = ctx.dims
+        dy = as_nhwc(dy)
+        B, H, W, _ = x.shape
+        dx = None
+        if ctx.needs_input_grad[0]:
+            sink = ctx.sink
+            running = sink.buf if sink is not None else None
+            in_place = (running is not None and running.is_contiguous() and running.dtype == torch.float32
+                        and tuple(running.shape) == (B, H, W, cin) and not is_limb_only(running))
+            if ctx.route == "taps":
+                wpd = ctx.cache.get(weights, co, True).dgrad
+                neg = sum_taps(ctx.geoms, negate=True)
+                if in_place:
+                    conv_taps(dy, wpd, neg, cin, out=running, residual=running, kind="dgrad")
+                else:
+                    dx = conv_taps(dy, wpd, neg, cin, kind="dgrad")
+            else:
+                acc = running if in_place else None
+                for i, (w, (k, dil, pad)) in enumerate(zip(weights, ctx.geoms)):
+                    wpd = ctx.cache.each[i].get_dgrad(w, cout_pad)
+                    got = conv_dgrad(dy, wpd, k, 1, dil, pad, cin, (H, W), accumulate=acc)
+                    if acc is None:
+                        acc = dx = got
+            if in_place:
+                _sink_done(sink)
+            else:
+                dx = _sink_give(sink, dx, True)
+        grads = [None] * len(ctx.params)
+        for i, (k, dil, pad) in enumerate(ctx.geoms):
+            if ctx.needs_input_grad[4 + i]:
+                into = _accumulate_target(ctx.params[i])
+                grads[i] = conv_wgrad(x, dy, k, 1, dil, pad, cout, cin, into=into, xlimbs=ctx.xlimbs)
+                if into is not None and _state.GRAD_READY is not None:
+                    _state.GRAD_READY(ctx.params[i])
+        if len(ctx.params) > n and any(ctx.needs_input_grad[4 + n:]):
+            db = colsum(dy)[:cout]  # one sum, handed to every bias
+            for i in range(n):
+                if ctx.needs_input_grad[4 + n + i]:
+                    grads[n + i] = db
+        return (dx, None, None, None, *grads)
+
+
 def _pad_vec(v, n):
     if v is None or v.numel() == n:
         return v
