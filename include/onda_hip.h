@@ -262,6 +262,16 @@ int64_t onda_bn_bwd_l2_ws(int64_t M, int C);
 int onda_bn_bwd_l2(const float* dout, const void* out, int64_t out_plane, const float* x, const float* mean, const float* invstd,
                    const float* gamma, const float* xhat_amax, void* dx, int64_t dx_plane, float* dx_amax, float* dres, float* ws,
                    int64_t M, int C, int relu, const uint8_t* relu_mask, int64_t split, int fuse_sums, onda_stream_t s);
+/* onda_bn_bwd_l2 for TRAINABLE affine parameters: the same arguments, launches and results, plus dgamma[C] = sum g * xhat and
+ * dbeta[C] = sum g over all M rows (either may be NULL; both NULL: exactly onda_bn_bwd_l2).  They are the two per-channel
+ * sums dx already needs: the sums pass writes them, by one workgroup per 16 channels that takes both row groups in turn
+ * (split > 0: xhat from each row's own group; the groups' double sums added group 0 + group 1 BEFORE the one rounding to
+ * fp32).  fp32 chunk partials combined in double in a fixed order: two runs give the same bits.  fuse_sums != 0 is
+ * supported (the first C / 16 workgroups of the apply launch then take both groups). */
+int onda_bn_bwd_affine_l2(const float* dout, const void* out, int64_t out_plane, const float* x, const float* mean,
+                          const float* invstd, const float* gamma, const float* xhat_amax, void* dx, int64_t dx_plane, float* dx_amax,
+                          float* dres, float* ws, int64_t M, int C, int relu, const uint8_t* relu_mask, int64_t split, int fuse_sums,
+                          float* dgamma, float* dbeta, onda_stream_t s);
 
 /* ---- a PAIR of train-mode BatchNorms whose outputs meet in one add: the first block of a ResNet layer,
  *   out = [relu](BN_a(xa) + BN_b(xb))   (a: the block's last conv, b: the shortcut conv; deeplabv2.py:53-68).
@@ -294,6 +304,12 @@ int onda_bn_pair_fwd_l2(const OndaBnSide* a, const OndaBnSide* b, float eps, int
 int64_t onda_bn_pair_bwd_l2_ws(int64_t M, int C);
 int onda_bn_pair_bwd_l2(const float* dout, const uint8_t* relu_mask, const OndaBnSide* a, const OndaBnSide* b, float* ws, int64_t M,
                         int C, int relu, int64_t split, onda_stream_t s);
+/* ... for trainable affine parameters: onda_bn_pair_bwd_l2 plus the four gradients [C], each may be NULL (all NULL: exactly
+ * onda_bn_pair_bwd_l2).  Both sides share g: dbeta_a = dbeta_b = sum g; dgamma_a / dgamma_b = sum g * xhat_a / sum g * xhat_b
+ * (rows 1 and 2 of the pair's sums).  Row groups, rounding and launches as onda_bn_bwd_affine_l2. */
+int onda_bn_pair_bwd_affine_l2(const float* dout, const uint8_t* relu_mask, const OndaBnSide* a, const OndaBnSide* b, float* ws,
+                               int64_t M, int C, int relu, int64_t split, float* dgamma_a, float* dbeta_a, float* dgamma_b,
+                               float* dbeta_b, onda_stream_t s);
 
 /* onda_conv2d_wgrad slabs with both operands pre-split: [pixel][channel] limb planes in, LDS-DMA + transposed LDS reads
  * (ds_read_b64_tr_b16), tiles of 256 x 128 or 128 x 128 (output x input channels) per tap and pixel range.
@@ -335,7 +351,7 @@ int onda_pack_weight_dgrad(const float* w_oihw, float* dst, int Cout, int Cin, i
  * f32[B,3,H,W] for the 7x7 stride-2 pad-3 stem (deeplabv2.py:283). */
 int onda_stem_im2col(const float* x_nchw, float* col, int B, int H, int W, int Ho, int Wo, int Kp, onda_stream_t s);
 
-/* ---- BatchNorm2d (eps 1e-5, affine frozen) ------------------------------------------------
+/* ---- BatchNorm2d (eps 1e-5; affine frozen, or trained through onda_bn_bwd_affine) ------------------------------------------------
  * train-mode semantics of torch.nn.BatchNorm2d as the reference toggles it
  * (adaptation_model.py:29-36, prototypes.py:104-110): */
 /* partials [tiles][2][C] -> mean[C], invstd[C]; if running_mean != NULL also the momentum
@@ -357,6 +373,14 @@ int onda_bn_fold(const float* gamma, const float* beta, const float* running_mea
 int64_t onda_bn_bwd_ws(int64_t M, int C);
 int onda_bn_bwd(const float* dout, const float* out, const float* x, const float* mean, const float* invstd,
                 const float* gamma, float* dx, float* dres, float* ws, int64_t M, int C, int relu, float* amax, onda_stream_t s);
+/* onda_bn_bwd for trainable affine parameters: the same launches and results, plus dgamma[C] = sum g * xhat and dbeta[C] =
+ * sum g (either may be NULL; both NULL: exactly onda_bn_bwd, and prev_ws must be NULL).  One call covers one row group.  With
+ * two groups the caller asks for no gradients in the first call and hands its workspace to the second (prev_ws, prev_M = the
+ * first group's rows): the finalize launch then sums the first group's chunk partials as well and writes group 0 + group 1,
+ * added in double in that order and rounded to fp32 once.  Deterministic (fixed order). */
+int onda_bn_bwd_affine(const float* dout, const float* out, const float* x, const float* mean, const float* invstd,
+                       const float* gamma, float* dx, float* dres, float* ws, int64_t M, int C, int relu, float* amax,
+                       const float* prev_ws, int64_t prev_M, float* dgamma, float* dbeta, onda_stream_t s);
 
 /* ---- GroupNorm(32 groups, eps 1e-5, trainable affine) [+ReLU] [* Dropout2d mask] -----------
  * deeplabv2.py:141,163,182 and :203,250 (feat is taken after the dropout). x[B][HW][C]

@@ -104,9 +104,11 @@ SIGNATURES = {
     "onda_bn_bwd_l2_ws": (L, [L, I]),
     "onda_bn_train_l2": (I, [P, P, I, F, P, P, P, P, P, F, P, P, P, P, I, P, P, P, L, I, P, L, I, I, P]),
     "onda_bn_bwd_l2": (I, [P, P, L, P, P, P, P, P, P, L, P, P, P, L, I, I, P, L, I, P]),
+    "onda_bn_bwd_affine_l2": (I, [P, P, L, P, P, P, P, P, P, L, P, P, P, L, I, I, P, L, I, P, P, P]),
     "onda_bn_pair_fwd_l2": (I, [POINTER(OndaBnSide), POINTER(OndaBnSide), F, I, P, P, L, I, P, L, I, P]),
     "onda_bn_pair_bwd_l2_ws": (L, [L, I]),
     "onda_bn_pair_bwd_l2": (I, [P, P, POINTER(OndaBnSide), POINTER(OndaBnSide), P, L, I, I, L, P]),
+    "onda_bn_pair_bwd_affine_l2": (I, [P, P, POINTER(OndaBnSide), POINTER(OndaBnSide), P, L, I, I, L, P, P, P, P, P]),
     "onda_conv2d_wgrad": (I, [P, P, P, I, I, POINTER(OndaConv), P]),
     "onda_wgrad_reduce": (I, [P, P, I, I, I, I, I, I, I, I, P]),
     "onda_pack_weight_fwd": (I, [P, P, I, I, I, I, I, P]),
@@ -118,6 +120,7 @@ SIGNATURES = {
     "onda_bn_fold": (I, [P, P, P, P, F, P, P, I, P]),
     "onda_bn_bwd_ws": (L, [L, I]),
     "onda_bn_bwd": (I, [P, P, P, P, P, P, P, P, P, L, I, I, P, P]),
+    "onda_bn_bwd_affine": (I, [P, P, P, P, P, P, P, P, P, L, I, I, P, P, L, P, P, P]),
     "onda_gn_ws": (L, [I, L, I]),
     "onda_gn_fwd": (I, [P, I, P, P, P, P, I, P, P, P, I, L, I, I, F, I, P, P]),
     "onda_gn_bwd": (I, [P, I, P, I, P, I, P, P, P, P, P, P, P, P, I, L, I, I, I, P]),

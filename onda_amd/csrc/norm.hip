@@ -254,6 +254,26 @@ __global__ __launch_bounds__(256) void pair_finalize_kernel(const float* __restr
   }
 }
 
+// pair_finalize_kernel with B = 1 when the affine parameters train: the same two sums into AB, and dbeta = sum g, dgamma =
+// sum g * xhat over ALL rows -- with two row groups the call of the second group hands in the first group's chunk partials
+// (`prev`, still in that call's workspace): both columns summed in double, group 0 + group 1 in that order, rounded to fp32 once
+__global__ __launch_bounds__(256) void bn_bwd_finalize_affine_kernel(const float* __restrict__ partials, int chunks,
+                                                                     const float* __restrict__ prev, int prev_chunks, int C,
+                                                                     float* __restrict__ AB, float* __restrict__ dgamma,
+                                                                     float* __restrict__ dbeta) {
+  const int ch = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (ch >= C) return;
+  double s1, s2, p1 = 0.0, p2 = 0.0;
+  table_column<true>(partials, chunks, 0, C, ch, s1, s2);
+  if (prev != nullptr) table_column<true>(prev, prev_chunks, 0, C, ch, p1, p2);
+  if ((threadIdx.x & 63) == 0) {
+    AB[ch] = (float)s1;
+    AB[(size_t)C + ch] = (float)s2;
+    if (dbeta) dbeta[ch] = (float)(p1 + s1);
+    if (dgamma) dgamma[ch] = (float)(p2 + s2);
+  }
+}
+
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dout,
                                                            const float* __restrict__ out, const float* __restrict__ x,
                                                            const float* __restrict__ mean,
@@ -464,20 +484,37 @@ int64_t onda_bn_bwd_ws(int64_t M, int C) {
   return (int64_t)p.chunks * 2 * C + 2 * C;
 }
 
-int onda_bn_bwd(const float* dout, const float* out, const float* x, const float* mean, const float* invstd,
-                const float* gamma, float* dx, float* dres, float* ws, int64_t M, int C, int relu, float* amax,
-                onda_stream_t s) {
+static int bn_bwd(const float* dout, const float* out, const float* x, const float* mean, const float* invstd,
+                  const float* gamma, float* dx, float* dres, float* ws, int64_t M, int C, int relu, float* amax,
+                  const float* prev_ws, int64_t prev_M, float* dgamma, float* dbeta, onda_stream_t s) {
   ONDA_REQUIRE(dout && x && mean && invstd && gamma && dx && ws && C % 4 == 0 && (!relu || out));
+  ONDA_REQUIRE(prev_ws == nullptr || (prev_M >= 1 && (dgamma || dbeta)));
   const ColPlan p = col_plan(1, M, C);
   float* sums = ws + (size_t)p.chunks * 2 * C;
   BnBwdRed f{dout, out, x, mean, invstd, dres, C, relu};
   int rc = launch_colreduce(f, 1, M, C, ws, p, ONDA_STREAM(s));
   if (rc) return rc;
-  hipLaunchKernelGGL(pair_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, ONDA_STREAM(s), ws, p.chunks, 1, C, sums);
+  if (dgamma || dbeta)
+    hipLaunchKernelGGL(bn_bwd_finalize_affine_kernel, dim3((C + 3) / 4), dim3(256), 0, ONDA_STREAM(s), ws, p.chunks, prev_ws,
+                       prev_ws ? col_plan(1, prev_M, C).chunks : 0, C, sums, dgamma, dbeta);
+  else
+    hipLaunchKernelGGL(pair_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, ONDA_STREAM(s), ws, p.chunks, 1, C, sums);
   const size_t total4 = (size_t)M * C / 4;
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, ONDA_STREAM(s), dout, out, x, mean,
                      invstd, gamma, sums, dx, total4, C, (float)(1.0 / (double)M), relu, amax);
   return ONDA_LAUNCH_RESULT();
+}
+
+int onda_bn_bwd(const float* dout, const float* out, const float* x, const float* mean, const float* invstd,
+                const float* gamma, float* dx, float* dres, float* ws, int64_t M, int C, int relu, float* amax,
+                onda_stream_t s) {
+  return bn_bwd(dout, out, x, mean, invstd, gamma, dx, dres, ws, M, C, relu, amax, nullptr, 0, nullptr, nullptr, s);
+}
+
+int onda_bn_bwd_affine(const float* dout, const float* out, const float* x, const float* mean, const float* invstd,
+                       const float* gamma, float* dx, float* dres, float* ws, int64_t M, int C, int relu, float* amax,
+                       const float* prev_ws, int64_t prev_M, float* dgamma, float* dbeta, onda_stream_t s) {
+  return bn_bwd(dout, out, x, mean, invstd, gamma, dx, dres, ws, M, C, relu, amax, prev_ws, prev_M, dgamma, dbeta, s);
 }
 
 int64_t onda_gn_ws(int B, int64_t HW, int C) {

@@ -613,12 +613,14 @@ struct BnBwdSumsArgs {
   const float *gamma, *invstd, *xhat_amax;
   float *sums, *dx_amax;
   int chunks0, groups;
+  float *dgamma, *dbeta;  // the affine gradients, either may be null: written by bn_bwd_sums_affine only
 };
-__device__ __forceinline__ void bn_bwd_sums_block(const BnBwdSumsArgs& a, const int bx, const int g) {
+// `sum`: the two double sums of this group's 16 channels, in the threads < 16 (zero elsewhere)
+__device__ __forceinline__ void bn_bwd_sums_block(const BnBwdSumsArgs& a, const int bx, const int g, double (&sum)[2]) {
   const int C = a.C;
   const int row0 = g == 0 ? 0 : a.chunks0, nrows = a.groups == 1 ? a.chunks : (g == 0 ? a.chunks0 : a.chunks - a.chunks0);
   const double inv_m = g == 0 ? a.inv_m0 : a.inv_m1;
-  double sum[2];
+  sum[0] = sum[1] = 0.0;
   float ext[1];
   reduce_rows16<3, 2, false>(a.partials + (size_t)row0 * 3 * C, nrows, C, bx * 16, sum, ext, nrows);
   const int ch = bx * 16 + threadIdx.x;
@@ -640,12 +642,37 @@ __device__ __forceinline__ void bn_bwd_sums_block(const BnBwdSumsArgs& a, const 
       atomicMax(reinterpret_cast<unsigned*>(a.dx_amax) + ((bx + 7 * g) & (ONDA_AMAX_SLOTS - 1)) * AMAX_STRIDE, __float_as_uint(m));
   }
 }
-__global__ __launch_bounds__(256) void bn_bwd_sums_l2_kernel(const BnBwdSumsArgs a) { bn_bwd_sums_block(a, blockIdx.x, blockIdx.y); }
+__global__ __launch_bounds__(256) void bn_bwd_sums_l2_kernel(const BnBwdSumsArgs a) {
+  double sum[2];
+  bn_bwd_sums_block(a, blockIdx.x, blockIdx.y, sum);
+}
+
+// pass 2 when the affine parameters train: ONE workgroup takes every row group of its 16 channels, group 0 then group 1, each
+// exactly as bn_bwd_sums_block leaves it (sums, dx bound), and writes dbeta = sum g and dgamma = sum g * xhat over all rows:
+// the groups' double sums added in that order and rounded to fp32 once (one group: the very floats of `sums`).
+__device__ __forceinline__ void bn_bwd_sums_affine(const BnBwdSumsArgs& a, const int bx) {
+  double tot[2] = {0.0, 0.0};
+#pragma unroll 1
+  for (int g = 0; g < a.groups; ++g) {
+    if (g) __syncthreads();  // (the reduction's and the bound's shared words)
+    double sum[2];
+    bn_bwd_sums_block(a, bx, g, sum);
+    tot[0] += sum[0];
+    tot[1] += sum[1];
+  }
+  const int ch = bx * 16 + threadIdx.x;
+  if (threadIdx.x < 16 && ch < a.C) {
+    if (a.dbeta) a.dbeta[ch] = (float)tot[0];
+    if (a.dgamma) a.dgamma[ch] = (float)tot[1];
+  }
+}
+__global__ __launch_bounds__(256) void bn_bwd_sums_affine_l2_kernel(const BnBwdSumsArgs a) { bn_bwd_sums_affine(a, blockIdx.x); }
 
 // pass 3: dx limbs.  group1_at > 0: the 8-channel items from there on belong to row group 1 (statistics at + C, sums at + 2C,
 // 1 / M of that group)
 // FUSED: the first `nfin` workgroups reduce the chunk partials first (bn_bwd_sums_block) and everybody waits for them
-template <bool FUSED>
+// AFFINE (with FUSED): they are one per 16 channels and take both row groups (bn_bwd_sums_affine)
+template <bool FUSED, bool AFFINE = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_l2_kernel(const float* __restrict__ dout, const _Float16* __restrict__ out,
                                                               size_t out_plane, const float* __restrict__ x,
                                                               const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -657,7 +684,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_l2_kernel(const float* __res
   if constexpr (FUSED) {
     const int nb = (C + 15) / 16;
     if ((int)blockIdx.x < nfin) {
-      bn_bwd_sums_block(fin, blockIdx.x % nb, blockIdx.x / nb);
+      if constexpr (AFFINE) {
+        bn_bwd_sums_affine(fin, blockIdx.x);
+      } else {
+        double sum[2];
+        bn_bwd_sums_block(fin, blockIdx.x % nb, blockIdx.x / nb, sum);
+      }
       grid_publish(fin.dx_amax);
     }
     grid_wait(fin.dx_amax, nfin);
@@ -768,12 +800,13 @@ struct BnBwdSumsPairArgs {
   BnBwdSumsSide a, b;
   float* sums;
   int chunks0, groups;
+  float *dgamma_a, *dgamma_b, *dbeta_a, *dbeta_b;  // the affine gradients, each may be null: bn_bwd_sums_pair_affine_l2_kernel
 };
-__global__ __launch_bounds__(256) void bn_bwd_sums_pair_l2_kernel(const BnBwdSumsPairArgs p) {
-  const int C = p.C, bx = blockIdx.x, g = blockIdx.y;
+__device__ __forceinline__ void bn_bwd_sums_pair_block(const BnBwdSumsPairArgs& p, const int bx, const int g, double (&sum)[3]) {
+  const int C = p.C;
   const int row0 = g == 0 ? 0 : p.chunks0, nrows = p.groups == 1 ? p.chunks : (g == 0 ? p.chunks0 : p.chunks - p.chunks0);
   const double inv_m = g == 0 ? p.inv_m0 : p.inv_m1;
-  double sum[3];
+  sum[0] = sum[1] = sum[2] = 0.0;
   float ext[1];
   reduce_rows16<4, 3, false>(p.partials + (size_t)row0 * 4 * C, nrows, C, bx * 16, sum, ext, nrows);
   const int ch = bx * 16 + threadIdx.x;
@@ -788,6 +821,31 @@ __global__ __launch_bounds__(256) void bn_bwd_sums_pair_l2_kernel(const BnBwdSum
   bn_bound_publish(bound_a * 1.000001f, p.a.dx_amax, bx, g);
   __syncthreads();  // (the publishing step's shared words)
   bn_bound_publish(bound_b * 1.000001f, p.b.dx_amax, bx, g);
+}
+__global__ __launch_bounds__(256) void bn_bwd_sums_pair_l2_kernel(const BnBwdSumsPairArgs p) {
+  double sum[3];
+  bn_bwd_sums_pair_block(p, blockIdx.x, blockIdx.y, sum);
+}
+// ... when the affine parameters train (see bn_bwd_sums_affine): one workgroup, both row groups; both sides share g, so
+// dbeta_a = dbeta_b = sum g; dgamma_a / dgamma_b from rows 1 / 2 of the sums
+__global__ __launch_bounds__(256) void bn_bwd_sums_pair_affine_l2_kernel(const BnBwdSumsPairArgs p) {
+  const int bx = blockIdx.x;
+  double tot[3] = {0.0, 0.0, 0.0};
+#pragma unroll 1
+  for (int g = 0; g < p.groups; ++g) {
+    if (g) __syncthreads();
+    double sum[3];
+    bn_bwd_sums_pair_block(p, bx, g, sum);
+#pragma unroll
+    for (int v = 0; v < 3; ++v) tot[v] += sum[v];
+  }
+  const int ch = bx * 16 + threadIdx.x;
+  if (threadIdx.x < 16 && ch < p.C) {
+    if (p.dbeta_a) p.dbeta_a[ch] = (float)tot[0];
+    if (p.dbeta_b) p.dbeta_b[ch] = (float)tot[0];
+    if (p.dgamma_a) p.dgamma_a[ch] = (float)tot[1];
+    if (p.dgamma_b) p.dgamma_b[ch] = (float)tot[2];
+  }
 }
 
 // pass 3: both conv gradients from one walk -- reads dout, the mask, xa and xb once, writes dx_a and dx_b as limb rows under
@@ -977,9 +1035,10 @@ int64_t onda_bn_bwd_l2_ws(int64_t M, int C) {
 
 /* fuse_sums != 0: the chunk partials are reduced by the first workgroups of the apply launch (two launches instead of three);
  * dx_amax's floats 1..3 then serve as the hand-over's counter (see onda_bn_train_l2) */
-int onda_bn_bwd_l2(const float* dout, const void* out, int64_t out_plane, const float* x, const float* mean, const float* invstd,
-                   const float* gamma, const float* xhat_amax, void* dx, int64_t dx_plane, float* dx_amax, float* dres, float* ws,
-                   int64_t M, int C, int relu, const uint8_t* relu_mask, int64_t split, int fuse_sums, onda_stream_t s) {
+static int bn_bwd_l2(const float* dout, const void* out, int64_t out_plane, const float* x, const float* mean, const float* invstd,
+                     const float* gamma, const float* xhat_amax, void* dx, int64_t dx_plane, float* dx_amax, float* dres, float* ws,
+                     int64_t M, int C, int relu, const uint8_t* relu_mask, int64_t split, int fuse_sums, float* dgamma, float* dbeta,
+                     onda_stream_t s) {
   ONDA_REQUIRE(dout && x && mean && invstd && gamma && xhat_amax && dx && dx_amax && ws && C % 32 == 0 && (!relu || out || relu_mask));
   ONDA_REQUIRE(256 % (C / 8) == 0 || (C / 8) % 256 == 0);
   ONDA_REQUIRE(split >= 0 && split < M);
@@ -993,8 +1052,23 @@ int onda_bn_bwd_l2(const float* dout, const void* out, int64_t out_plane, const 
                      (size_t)out_plane, x, mean, invstd, dres, M, C, relu, p.cx, p.rows_per_chunk, ws, relu_mask, split, chunks0);
   const double inv_m0 = 1.0 / (double)(split > 0 ? split : M), inv_m1 = 1.0 / (double)(M - split);
   const int groups = split > 0 ? 2 : 1;
-  const BnBwdSumsArgs fin{ws, chunks, C, inv_m0, inv_m1, gamma, invstd, xhat_amax, sums, dx_amax, chunks0, groups};
+  const BnBwdSumsArgs fin{ws, chunks, C, inv_m0, inv_m1, gamma, invstd, xhat_amax, sums, dx_amax, chunks0, groups, dgamma, dbeta};
   const size_t total8 = (size_t)M * C / 8;
+  if (dgamma || dbeta) {  // the same launches, the sums pass by one workgroup per 16 channels (bn_bwd_sums_affine)
+    const int nfin = (C + 15) / 16;
+    if (fuse_sums) {
+      const unsigned grid = ew_grid(total8) > (unsigned)nfin ? ew_grid(total8) : (unsigned)nfin;
+      hipLaunchKernelGGL((bn_bwd_apply_l2_kernel<true, true>), dim3(grid), dim3(256), 0, st, dout, static_cast<const _Float16*>(out),
+                         (size_t)out_plane, x, mean, invstd, gamma, sums, static_cast<_Float16*>(dx), (size_t)dx_plane, dx_amax,
+                         total8, C, (float)inv_m0, relu, relu_mask, (size_t)split * C / 8, (float)inv_m1, fin, nfin);
+      return ONDA_LAUNCH_RESULT();
+    }
+    hipLaunchKernelGGL(bn_bwd_sums_affine_l2_kernel, dim3(nfin), dim3(256), 0, st, fin);
+    hipLaunchKernelGGL(bn_bwd_apply_l2_kernel<false>, dim3(ew_grid(total8)), dim3(256), 0, st, dout, static_cast<const _Float16*>(out),
+                       (size_t)out_plane, x, mean, invstd, gamma, sums, static_cast<_Float16*>(dx), (size_t)dx_plane, dx_amax, total8,
+                       C, (float)inv_m0, relu, relu_mask, (size_t)split * C / 8, (float)inv_m1, BnBwdSumsArgs{}, 0);
+    return ONDA_LAUNCH_RESULT();
+  }
   if (fuse_sums) {
     const int nfin = (C + 15) / 16 * groups;
     const unsigned grid = ew_grid(total8) > (unsigned)nfin ? ew_grid(total8) : (unsigned)nfin;
@@ -1008,6 +1082,21 @@ int onda_bn_bwd_l2(const float* dout, const void* out, int64_t out_plane, const 
                      (size_t)out_plane, x, mean, invstd, gamma, sums, static_cast<_Float16*>(dx), (size_t)dx_plane, dx_amax, total8,
                      C, (float)inv_m0, relu, relu_mask, (size_t)split * C / 8, (float)inv_m1, BnBwdSumsArgs{}, 0);
   return ONDA_LAUNCH_RESULT();
+}
+
+int onda_bn_bwd_l2(const float* dout, const void* out, int64_t out_plane, const float* x, const float* mean, const float* invstd,
+                   const float* gamma, const float* xhat_amax, void* dx, int64_t dx_plane, float* dx_amax, float* dres, float* ws,
+                   int64_t M, int C, int relu, const uint8_t* relu_mask, int64_t split, int fuse_sums, onda_stream_t s) {
+  return bn_bwd_l2(dout, out, out_plane, x, mean, invstd, gamma, xhat_amax, dx, dx_plane, dx_amax, dres, ws, M, C, relu, relu_mask,
+                   split, fuse_sums, nullptr, nullptr, s);
+}
+
+int onda_bn_bwd_affine_l2(const float* dout, const void* out, int64_t out_plane, const float* x, const float* mean,
+                          const float* invstd, const float* gamma, const float* xhat_amax, void* dx, int64_t dx_plane, float* dx_amax,
+                          float* dres, float* ws, int64_t M, int C, int relu, const uint8_t* relu_mask, int64_t split, int fuse_sums,
+                          float* dgamma, float* dbeta, onda_stream_t s) {
+  return bn_bwd_l2(dout, out, out_plane, x, mean, invstd, gamma, xhat_amax, dx, dx_plane, dx_amax, dres, ws, M, C, relu, relu_mask,
+                   split, fuse_sums, dgamma, dbeta, s);
 }
 
 // ---- the pair (see include/onda_hip.h) ----------------------------------------------------------------------------------------
@@ -1044,8 +1133,9 @@ int64_t onda_bn_pair_bwd_l2_ws(int64_t M, int C) {
   return (int64_t)(p.chunks + 1) * 4 * C + 6 * C;  // (+1 chunk row: two row groups round up separately; sums[2][3][C])
 }
 
-int onda_bn_pair_bwd_l2(const float* dout, const uint8_t* relu_mask, const OndaBnSide* a, const OndaBnSide* b, float* ws, int64_t M,
-                        int C, int relu, int64_t split, onda_stream_t s) {
+static int bn_pair_bwd_l2(const float* dout, const uint8_t* relu_mask, const OndaBnSide* a, const OndaBnSide* b, float* ws, int64_t M,
+                          int C, int relu, int64_t split, float* dgamma_a, float* dbeta_a, float* dgamma_b, float* dbeta_b,
+                          onda_stream_t s) {
   ONDA_REQUIRE(dout && pair_side_ok(a, true) && pair_side_ok(b, true) && ws && M >= 1 && C >= 32 && C % 32 == 0 && (!relu || relu_mask));
   ONDA_REQUIRE(256 % (C / 8) == 0);
   ONDA_REQUIRE(split >= 0 && split < M);
@@ -1061,15 +1151,30 @@ int onda_bn_pair_bwd_l2(const float* dout, const uint8_t* relu_mask, const OndaB
                      b->invstd, M, C, relu, p.cx, p.rows_per_chunk, ws, relu_mask, split, chunks0);
   const double inv_m0 = 1.0 / (double)(split > 0 ? split : M), inv_m1 = 1.0 / (double)(M - split);
   const int groups = split > 0 ? 2 : 1;
-  hipLaunchKernelGGL(bn_bwd_sums_pair_l2_kernel, dim3((C + 15) / 16, groups), dim3(256), 0, st,
-                     BnBwdSumsPairArgs{ws, chunks, C, inv_m0, inv_m1, BnBwdSumsSide{a->gamma, a->invstd, a->xhat_amax, a->dx_amax},
-                                       BnBwdSumsSide{b->gamma, b->invstd, b->xhat_amax, b->dx_amax}, sums, chunks0, groups});
+  const BnBwdSumsPairArgs fin{ws, chunks, C, inv_m0, inv_m1, BnBwdSumsSide{a->gamma, a->invstd, a->xhat_amax, a->dx_amax},
+                              BnBwdSumsSide{b->gamma, b->invstd, b->xhat_amax, b->dx_amax}, sums, chunks0, groups,
+                              dgamma_a, dgamma_b, dbeta_a, dbeta_b};
+  if (dgamma_a || dgamma_b || dbeta_a || dbeta_b)
+    hipLaunchKernelGGL(bn_bwd_sums_pair_affine_l2_kernel, dim3((C + 15) / 16), dim3(256), 0, st, fin);
+  else
+    hipLaunchKernelGGL(bn_bwd_sums_pair_l2_kernel, dim3((C + 15) / 16, groups), dim3(256), 0, st, fin);
   const size_t total8 = (size_t)M * C / 8;
   hipLaunchKernelGGL(bn_bwd_apply_pair_l2_kernel, dim3(ew_grid(total8)), dim3(256), 0, st, dout,
                      BnBwdPairSide{a->x, a->mean, a->invstd, a->gamma, static_cast<_Float16*>(a->dx), a->dx_amax},
                      BnBwdPairSide{b->x, b->mean, b->invstd, b->gamma, static_cast<_Float16*>(b->dx), b->dx_amax}, sums, total8, C,
                      (float)inv_m0, (float)inv_m1, relu, relu_mask, (size_t)split * C / 8);
   return ONDA_LAUNCH_RESULT();
+}
+
+int onda_bn_pair_bwd_l2(const float* dout, const uint8_t* relu_mask, const OndaBnSide* a, const OndaBnSide* b, float* ws, int64_t M,
+                        int C, int relu, int64_t split, onda_stream_t s) {
+  return bn_pair_bwd_l2(dout, relu_mask, a, b, ws, M, C, relu, split, nullptr, nullptr, nullptr, nullptr, s);
+}
+
+int onda_bn_pair_bwd_affine_l2(const float* dout, const uint8_t* relu_mask, const OndaBnSide* a, const OndaBnSide* b, float* ws,
+                               int64_t M, int C, int relu, int64_t split, float* dgamma_a, float* dbeta_a, float* dgamma_b,
+                               float* dbeta_b, onda_stream_t s) {
+  return bn_pair_bwd_l2(dout, relu_mask, a, b, ws, M, C, relu, split, dgamma_a, dbeta_a, dgamma_b, dbeta_b, s);
 }
 
 }  // extern "C"

@@ -4,7 +4,7 @@ import os
 import sys
 
 _MODULES = [
-    "framework", "framework.model", "framework.model.deeplabv2", "framework.model.discriminator", "framework.handlers",
+    "framework", "framework.model", "framework.model.deeplabv2", "framework.model.deeplabv2_proda", "framework.model.discriminator", "framework.handlers",
     "framework.handlers.model_handler", "framework.handlers.adaptation_method_handler",
     "framework.utils", "framework.utils.func", "framework.utils.loss", "framework.utils.monitoring",
     "framework.domain_adaptation", "framework.domain_adaptation.methods",

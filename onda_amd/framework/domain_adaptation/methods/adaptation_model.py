@@ -18,6 +18,7 @@ from torch import nn
 
 from onda_amd import ops
 from onda_amd.config import unset
+from onda_amd.framework.model.deeplabv2 import require_single_gpu_affine
 from onda_amd.optim import ReplaySGD
 from onda_amd.framework.utils.func import lr_poly, per_class_iu
 from onda_amd.framework.utils.monitoring import ECE
@@ -106,6 +107,7 @@ class da_model:
             # methods fail with a TypeError at their first step): such a model trains through segmentation.train
             raise NotImplementedError("onda_amd: the adaptation methods need a model with features (MODEL.CLASSIFIER: 'ProDA'); "
                                       "a 'normal'-head model is trained and evaluated by segmentation.train / SegmentationTrainer")
+        require_single_gpu_affine(model, "an adaptation method")
         self.model, self.cfg, self.cfg_spec = model, cfg, cfg_spec
         self.device = cfg.OTHERS.DEVICE
         self.bn = batchnorm_stats(model)

@@ -219,8 +219,7 @@ class online_proDA(da_model):
             previous.close()
             if ops.GRAD_READY == previous.grad_ready:
                 ops.GRAD_READY = None
-        self._grad_sync = odist.GradSync(self.model, tail_floats=self._tail_size(),
-                                         skip=(lambda name: name.startswith("layer5.")) if not self.model.multi_level else None)
+        self._grad_sync = odist.GradSync(self.model, tail_floats=self._tail_size(), skip=deeplabv2.unused_head_skip(self.model))
         model.__dict__["_onda_grad_sync"] = self._grad_sync
         if self._grad_sync.active:
             ops.GRAD_READY = self._grad_sync.grad_ready

@@ -18,6 +18,7 @@ from onda_amd import dist as odist
 from onda_amd import logging as olog
 from onda_amd import ops
 from onda_amd.config import unset
+from onda_amd.framework.model.deeplabv2 import require_single_gpu_affine, unused_head_skip
 from onda_amd.framework.utils.func import lr_poly, per_class_iu
 from onda_amd.optim import ReplaySGD
 
@@ -26,6 +27,7 @@ class SegmentationTrainer:
     def __init__(self, model, cfg, cfg_spec):
         if not unset(cfg.DOMAIN_ANALYSIS):
             raise NotImplementedError("onda_amd: the DOMAIN_ANALYSIS variant of segmentation.train is outside the hot path")
+        require_single_gpu_affine(model, "SegmentationTrainer")
         self.model, self.cfg, self.spec = model, cfg, cfg_spec
         self.device = cfg.OTHERS.DEVICE
         width, height = cfg.SCHEME.RESOLUTION
@@ -39,7 +41,7 @@ class SegmentationTrainer:
         previous = model.__dict__.get("_onda_grad_sync")
         if previous is not None:
             previous.close()
-        skip = (lambda name: name.startswith("layer5.")) if not getattr(model, "multi_level", True) else None
+        skip = unused_head_skip(model)
         self._float_buffers = [b for b in model.buffers() if b.dtype == torch.float32]  # BatchNorm running statistics
         self._grad_sync = odist.GradSync(model, tail_floats=sum(b.numel() for b in self._float_buffers), skip=skip)
         model.__dict__["_onda_grad_sync"] = self._grad_sync

@@ -108,6 +108,28 @@ def conv_bn(conv, bn, x, relu, residual=None):
     return y
 
 
+def trains_bn_affine(model):
+    """Does a BatchNorm2d of `model` have a trainable affine parameter (``norm_grad=True``, the ProDA ResNet-101)?"""
+    return any(p.requires_grad for m in model.modules() if isinstance(m, nn.BatchNorm2d) for p in m.parameters(recurse=False))
+
+
+def require_single_gpu_affine(model, who):
+    """Trainable BatchNorm affine parameters are a one-GPU feature: with ``onda_amd.dist`` active `who` refuses such a model."""
+    from onda_amd import dist as odist
+    if odist.is_on() and trains_bn_affine(model):
+        raise NotImplementedError(f"onda_amd: {who} on a model with trainable BatchNorm affine parameters and several ranks: the "
+                                  "flat-buffer gradient exchange is untested for these parameters (train them on one GPU, or "
+                                  "freeze them: freeze_bn=True / norm_grad=False)")
+
+
+def unused_head_skip(model):
+    """For the gradient exchange: the name filter of the auxiliary head that never runs (``layer5`` of a ResNetMulti with
+    ``multi_level`` off), or None -- ``layer5`` of the ProDA ResNet-101 is its main head."""
+    if getattr(model, "multi_level", True) or getattr(model, "main_head", "layer6") == "layer5":
+        return None
+    return lambda name: name.startswith("layer5.")
+
+
 def _running(bn):
     """The running buffers a train-mode BatchNorm moves (None: ``track_running_stats`` off)."""
     if bn.momentum is None:
@@ -217,7 +239,7 @@ def force_mask(mask):
 
 def draw_mask(model, batch, device):
     """The Dropout2d mask the next training-mode forward of `model` would draw (None when dropout is inactive)."""
-    head = model.layer6.head[0]
+    head = getattr(model, getattr(model, "main_head", "layer6")).head[0]
     if not (head.training and head.p > 0):
         return None
     return drop_mask_fn(batch, 256, head.p, device).reshape(batch, 256).contiguous()

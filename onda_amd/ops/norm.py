@@ -17,7 +17,8 @@ from .conv import _sink_give, _sink_of, colsum
 
 class BNTrainFn(torch.autograd.Function):
     """Batch-statistics BatchNorm (+residual, +ReLU) on a conv output whose sum / sum-of-squares
-    partials came out of the conv epilogue.  Affine parameters are frozen (no dgamma/dbeta).
+    partials came out of the conv epilogue.  dgamma / dbeta only where autograd asks (``onda_bn_bwd_affine``: the two sums
+    the data gradient needs anyway, over both row groups); frozen affine parameters make the calls they always made.
     Under ``ops.row_groups`` (the stem's BatchNorm in the paired student pass) the two row groups are normalised one
     after the other on their row ranges of the same buffers; only the second group moves the running statistics."""
 
@@ -85,17 +86,27 @@ class BNTrainFn(torch.autograd.Function):
         dres = None
         if need_res:
             dres = torch.empty_like(y) if ctx.relu else dout
+        dg = torch.empty(C, device=y.device, dtype=torch.float32) if ctx.needs_input_grad[2] else None
+        db = torch.empty(C, device=y.device, dtype=torch.float32) if ctx.needs_input_grad[3] else None
+        affine = dg is not None or db is not None
+        prev, last = None, len(ctx.groups) - 1
         for g, (r0, rows) in enumerate(ctx.groups):
             ws = torch.empty(query("onda_bn_bwd_ws", rows, C), device=y.device, dtype=torch.float32)
             off = 4 * r0 * C
-            call("onda_bn_bwd", dout.data_ptr() + off, out.data_ptr() + off if out is not None else None, y.data_ptr() + off,
-                 _p(mean[g]), _p(invstd[g]), _p(gamma), dx.data_ptr() + off,
-                 dres.data_ptr() + off if (need_res and ctx.relu) else None, _p(ws), rows, C, int(ctx.relu), _p(amax), _stream())
+            args = (dout.data_ptr() + off, out.data_ptr() + off if out is not None else None, y.data_ptr() + off,
+                    _p(mean[g]), _p(invstd[g]), _p(gamma), dx.data_ptr() + off,
+                    dres.data_ptr() + off if (need_res and ctx.relu) else None, _p(ws), rows, C, int(ctx.relu), _p(amax))
+            if affine and g == last:
+                # the last group's call writes the gradients over all rows: it sums the group before from that call's workspace
+                call("onda_bn_bwd_affine", *args, _p(prev), ctx.groups[0][1] if prev is not None else 0, _p(dg), _p(db), _stream())
+            else:
+                call("onda_bn_bwd", *args, _stream())
+            prev = ws
         if amax is not None:
             tag_amax(dx, amax)  # dx is the dy of the conv below: data gradient and weight gradient read it
         if need_res:
             dres = _sink_give(ctx.res_sink, dres, ctx.relu)
-        return dx, None, None, None, dres, None, None, None
+        return dx, None, dg, db, dres, None, None, None
 
 
 class BNTrainLimbFn(torch.autograd.Function):
@@ -104,7 +115,7 @@ class BNTrainLimbFn(torch.autograd.Function):
     read limb planes -- so no fp32 copy is written.  `stats`: the conv epilogue's [tiles][4][C] partials (sum, sum of
     squares, min, max); the extrema bound max|out| before the apply pass (csrc/norm_l2.hip).  Backward: dout is an
     ordinary fp32 tensor, the gradient of the conv output goes out as limb planes again (consumed by the data- and
-    weight-gradient kernels only)."""
+    weight-gradient kernels only); dgamma / dbeta only where autograd asks (``onda_bn_bwd_affine_l2``, the same launches)."""
 
     @staticmethod
     def forward(ctx, y, stats, gamma, beta, residual, relu, running, momentum):
@@ -169,14 +180,20 @@ class BNTrainLimbFn(torch.autograd.Function):
         if need_res:
             dres = torch.empty_like(y) if ctx.relu else dout
         ol = ctx.out_limbs
-        call("onda_bn_bwd_l2", _p(dout), _p(ol.planes) if ol is not None else None, ol.plane if ol is not None else 0, _p(y),
-             _p(mean), _p(invstd), _p(gamma), _p(xhat_amax), _p(planes), M * C, _p(dx_amax),
-             _p(dres) if (need_res and ctx.relu) else None, _p(ws), M, C, int(ctx.relu), _p(ctx.relu_mask), ctx.split,
-             int(_state.FUSE_BN_FINALIZE), _stream())
+        dg = torch.empty(C, device=dev, dtype=torch.float32) if ctx.needs_input_grad[2] else None
+        db = torch.empty(C, device=dev, dtype=torch.float32) if ctx.needs_input_grad[3] else None
+        args = (_p(dout), _p(ol.planes) if ol is not None else None, ol.plane if ol is not None else 0, _p(y),
+                _p(mean), _p(invstd), _p(gamma), _p(xhat_amax), _p(planes), M * C, _p(dx_amax),
+                _p(dres) if (need_res and ctx.relu) else None, _p(ws), M, C, int(ctx.relu), _p(ctx.relu_mask), ctx.split,
+                int(_state.FUSE_BN_FINALIZE))
+        if dg is not None or db is not None:
+            call("onda_bn_bwd_affine_l2", *args, _p(dg), _p(db), _stream())
+        else:
+            call("onda_bn_bwd_l2", *args, _stream())
         dx = limb_only((B, H, W, C), dev, Limbs(planes, dx_amax, C, M * C))
         if need_res:
             dres = _sink_give(ctx.res_sink, dres, ctx.relu)
-        return dx, None, None, None, dres, None, None, None
+        return dx, None, dg, db, dres, None, None, None
 
 
 def bn_pair_ok(y_a, stats_a, y_b, stats_b):
@@ -193,11 +210,12 @@ def _bn_side(y, stats, tile_rows, mean, invstd, xhat_amax, running, momentum, ga
 
 
 class BNPairLimbFn(torch.autograd.Function):
-    """out = [relu](BN_a(y_a) + BN_b(y_b)), both train-mode with frozen affine parameters, as limb rows only: what
+    """out = [relu](BN_a(y_a) + BN_b(y_b)), both train-mode, as limb rows only: what
     ``BNTrainLimbFn(y_a, ..., residual=BNTrainLimbFn(y_b, ...))`` returns, without the shortcut's limb rows in between and,
     backward, without the fp32 copy of the masked gradient.  The shortcut term is added in fp32 instead of from two f16 limbs.
     Row groups and running statistics as BNTrainLimbFn has them, for both sides.  Backward returns the two conv-output
-    gradients as limb-only tensors; there is no residual to hand a gradient to."""
+    gradients as limb-only tensors; there is no residual to hand a gradient to.  The four affine gradients only where
+    autograd asks (``onda_bn_pair_bwd_affine_l2``, the same launches): both sides share g, so dbeta_a = dbeta_b."""
 
     @staticmethod
     def forward(ctx, y_a, stats_a, gamma_a, beta_a, running_a, momentum_a, y_b, stats_b, gamma_b, beta_b, running_b, momentum_b, relu):
@@ -239,9 +257,15 @@ class BNPairLimbFn(torch.autograd.Function):
         amax = [amax_slot(dev) for _ in range(2)]
         sa = _bn_side(y_a, None, 0, stat[0], stat[1], stat[2], None, 0.0, gamma_a, None, dx[0], amax[0])
         sb = _bn_side(y_b, None, 0, stat[3], stat[4], stat[5], None, 0.0, gamma_b, None, dx[1], amax[1])
-        call("onda_bn_pair_bwd_l2", _p(dout), _p(ctx.relu_mask), byref(sa), byref(sb), _p(ws), M, C, int(ctx.relu), ctx.split, _stream())
+        # (gamma_a, beta_a, gamma_b, beta_b: inputs 2, 3, 8, 9)
+        aff = [torch.empty(C, device=dev, dtype=torch.float32) if ctx.needs_input_grad[i] else None for i in (2, 3, 8, 9)]
+        args = (_p(dout), _p(ctx.relu_mask), byref(sa), byref(sb), _p(ws), M, C, int(ctx.relu), ctx.split)
+        if any(t is not None for t in aff):
+            call("onda_bn_pair_bwd_affine_l2", *args, *[_p(t) for t in aff], _stream())
+        else:
+            call("onda_bn_pair_bwd_l2", *args, _stream())
         da, db = (limb_only((B, H, W, C), dev, Limbs(dx[i], amax[i], C, M * C)) for i in range(2))
-        return da, None, None, None, None, None, db, None, None, None, None, None, None
+        return da, None, aff[0], aff[1], None, None, db, None, aff[2], aff[3], None, None, None
 
 
 def fold_bounds(weight, scale, shift):
