@@ -6,7 +6,9 @@
 //
 // Bit-exactness.  The reference computes these statistics in float64 on the host with numpy; the arithmetic here repeats
 // numpy's ORDER of operations, so the trajectories of fixture G5 are reproduced to the last bit:
-//   * avg     = np.median(window): the middle element, or (lo + hi) / 2 of the two middle ones;
+//   * avg     = np.median(window): the middle element, or (lo + hi) / 2 of the two middle ones -- and NaN while the window
+//               holds a NaN sample, as np.median gives it (the "median" trend's two levels likewise, each over its own
+//               sub-window): the machine then sees neither strict test fire and falls back to current_dev, as on the host;
 //   * exp     = (1 - c) * exp + c * v, products rounded before the sum (no fused multiply-add);
 //   * dev_avg = level(w[1:]) - level(w[:-1]) once the window is full, level(w) = np.sum(taps * w) / np.sum(taps) with
 //               numpy's pairwise summation (np_pairwise_sum below: 8 running partial sums over blocks of at most 128);
@@ -70,7 +72,9 @@ __device__ void rank_sort(const double* w, double* sorted, int n) {
   }
   __syncthreads();
 }
+// np.median: NaN while the span holds one.  NaNs sort last, so the last slot tells.
 __device__ double median_of_sorted(const double* s, int n) {
+  if (s[n - 1] != s[n - 1]) return s[n - 1];
   return (n & 1) ? s[n / 2] : ddiv(dadd(s[n / 2 - 1], s[n / 2]), 2.0);
 }
 

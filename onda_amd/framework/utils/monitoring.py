@@ -250,7 +250,11 @@ class ECE:
 class DeviceSwitch:
     """``Monitor`` for ONE series plus ``model_select`` (prototypes_hybrid_switch.py:22-34), kept and advanced on the
     GPU: ``step(sample)`` = add the sample, take median / exponential average / trend, run the two-state machine -- one
-    small launch, no read-back.  ``flag`` (device int32[1]) is the machine's state: 0 static, 1 dynamic."""
+    small launch, no read-back.  ``flag`` (device int32[1]) is the machine's state: 0 static, 1 dynamic.
+
+    A NaN sample makes the median (and every level of the trend that spans it) NaN for as long as it is in the window,
+    as ``Monitor.avg`` / ``dev_avg`` (``np.median``, ``np.sum``) do: neither gray-area test fires and the machine follows
+    ``current_dev`` for those ``limit`` steps, on the device as on the host (tests/test_switch_parity.py)."""
 
     def __init__(self, device, limit, exp_const=0.01, dev_func="hamming", gray_area=(0.84, 0.88), dev_threshold=0.0002,
                  start=0, use_exp=False):

@@ -310,16 +310,22 @@ def upsample_ece(out_or_rows, labels, table, bins, probs=False, hist=None, num_c
 
 # ------------------------------------------------------------------------------- device-side switch
 def select_prior(flag, a, wa, b, wb):
-    """flag ? wb * b : wa * a, elementwise, as a true select (`b` may be garbage when flag == 0)."""
-    out = torch.empty_like(a)
-    call("onda_select_prior", _p(flag), _p(a.contiguous()), float(wa), _p(b.contiguous()), float(wb), _p(out), a.numel(), _stream())
+    """flag ? wb * b : wa * a, elementwise, as a true select (`b` may be garbage when flag == 0).  `a` and `b` may be any
+    views of one shape; the result is contiguous in that shape (empty_like would keep a dense permuted view's strides,
+    which the kernel's flat order does not follow)."""
+    out = torch.empty(a.shape, device=a.device, dtype=a.dtype)
+    # the contiguous copies are held until the launch is enqueued: as temporaries, a's block would be freed at once and handed
+    # to b's copy, and the kernel would read b through both pointers
+    ac, bc = a.contiguous(), b.contiguous()
+    call("onda_select_prior", _p(flag), _p(ac), float(wa), _p(bc), float(wb), _p(out), a.numel(), _stream())
     return out
 
 
 def gate_scalar(flag, v):
     """flag ? v : NaN as a device scalar."""
     out = torch.empty(1, device=v.device, dtype=torch.float32)
-    call("onda_gate_scalar", _p(flag), _p(v.detach().reshape(1).float()), _p(out), _stream())
+    v32 = v.detach().reshape(1).float()  # (held until the launch is enqueued: a float64 scalar is a copy)
+    call("onda_gate_scalar", _p(flag), _p(v32), _p(out), _stream())
     return out[0]
 
 
