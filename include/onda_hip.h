@@ -536,6 +536,29 @@ int onda_target_loss_bwd(const float* logits, int ldl, const int64_t* labels, in
                          float w_reg, float w_js, const float* result, const float* gscale, float* dlogits, int64_t N,
                          int K, onda_stream_t s);
 
+/* ---- soft-label target loss (SOFT_LABELS; loss.py:12-13 CXE, :32-34, :95-99 soft RCE; func.py:35-42; prototypes.py:305-322) ----
+ * The target is the prototype soft map soft f32[N][K] (rows of stride lds >= K) instead of hard labels.  Three properties of
+ * the reference's branch, kept as they are:
+ *  1. CE reads the RAW logits x: ce = -sum_pixels sum_k tc_k * log(x_k + 1e-6) / N, the add in float32.  Every entry is
+ *     formed, whatever tc_k is: x_k + 1e-6 < 0 gives NaN (0 * NaN = NaN), x_k + 1e-6 == 0 gives 0 * -inf = NaN or -(-inf), so
+ *     over ordinary logits ce and total are NaN while the gradient, -(g*w_ce/N * tc_k) / (x_k + 1e-6) as written (0/0 = NaN,
+ *     tc/0 = -inf exactly where the reference's are), stays finite elsewhere.
+ *  2. ce_trunc != 0: tc = truncf(t), the `.long()` that func.loss_calc applies on the step's path -- 1 only where a soft value
+ *     is exactly 1.0, else 0.  ce_trunc == 0: tc = t, cross_entropy_2d(soft=True) called directly.
+ *  3. RCE uses the real soft values: rce = -sum_pixels sum_k p_k * log(t_k + 1e-6) / N, p = softmax(x); its gradient is
+ *     -(g*w_rce/N) * p_k * (c_k - sum_j p_j c_j), c = log(t + 1e-6).
+ * Nothing is thresholded or ignored; the regulariser takes the selectors of onda_target_loss_* and runs over every pixel.
+ * fwd: result (8 floats) = {ce, rce, reg, total, 0, 0, 0, 0}, total = the sum of w * term over the terms whose weight is
+ * non-zero; ws: 8*(N/256+1).  bwd: dlogits = g * d(total)/dlogits with the same selectors and weights; columns K..ldl-1 are
+ * zeroed; both normalisers are N, so nothing of the forward pass is needed.  A term whose weight is 0 enters neither total
+ * nor the gradient: with w_ce == 0 both are finite over negative logits and at a pole.  Reductions in a fixed order.
+ * ONDA_EINVAL before any launch: a null pointer (gscale may be NULL: g = 1), K outside 1..32, ldl < K, lds < K, ldl > 32 (bwd),
+ * an unknown selector; ONDA_EALIGN: a pointer that is not at a float boundary. */
+int onda_soft_loss_fwd(const float* logits, int ldl, const float* soft, int lds, int ce_trunc, int regularizer, float w_ce,
+                       float w_rce, float w_reg, float* result, float* ws, int64_t N, int K, onda_stream_t s);
+int onda_soft_loss_bwd(const float* logits, int ldl, const float* soft, int lds, int ce_trunc, int regularizer, float w_ce,
+                       float w_rce, float w_reg, const float* gscale, float* dlogits, int64_t N, int K, onda_stream_t s);
+
 /* ---- prototypes (framework/domain_adaptation/methods/prototype_handler.py) ----------------
  * sigma (:53-60) from the state; then per pixel (:111-166): D[k] = || (f - p_k) / sigma ||
  * (mahalanobis=1) or || f - p_k ||, minus its minimum; P = softmax(-D/tau); P *= prior;

@@ -155,6 +155,8 @@ SIGNATURES = {
     "onda_seg_loss_bwd": (I, [P, I, P, P, P, F, F, F, P, L, I, P]),
     "onda_target_loss_fwd": (I, [P, I, P, I, F, F, F, F, P, P, L, I, P]),
     "onda_target_loss_bwd": (I, [P, I, P, I, F, F, F, F, P, P, P, L, I, P]),
+    "onda_soft_loss_fwd": (I, [P, I, P, I, I, I, F, F, F, P, P, L, I, P]),
+    "onda_soft_loss_bwd": (I, [P, I, P, I, I, I, F, F, F, P, P, L, I, P]),
     "onda_proto_sigma": (I, [P, P, P, P, I, I, P]),
     "onda_proto_assign_blocks": (I, [L]),
     "onda_proto_assign": (I, [P, I, P, I, P, P, I, F, F, P, P, P, P, L, I, I, P]),

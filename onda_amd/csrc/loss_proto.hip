@@ -342,6 +342,120 @@ __global__ __launch_bounds__(256) void target_loss_bwd_kernel(const float* __res
   }
 }
 
+// ---- soft-label CE + RCE + (MRKLD | MRENT) ---------------------------------------------------------
+// The SOFT_LABELS branch of prototypes.py:305-322 (loss.py:12-13, :32-34, :95-99): the target t[N][K] is the prototype soft
+// map.  CE = -sum_k tc_k log(x_k + 1e-6) / N over the RAW logits x, as the reference writes it -- every entry is formed, so
+// a negative x_k + 1e-6 gives NaN and a zero one -inf whatever tc_k is (0 * NaN = NaN) -- with tc = trunc(t) on the step's
+// path (func.loss_calc's .long()) and tc = t for cross_entropy_2d called directly.  RCE = -sum_k p_k log(t_k + 1e-6) / N
+// with the real soft values.  The regulariser is target_loss's.  Both normalisers are N: the backward pass needs nothing
+// from the forward pass.
+__device__ __forceinline__ float soft_ce_target(float t, int ce_trunc) { return ce_trunc ? truncf(t) : t; }
+
+__global__ __launch_bounds__(256) void soft_loss_fwd_kernel(const float* __restrict__ logits, int ldl,
+                                                            const float* __restrict__ soft, int lds, int ce_trunc,
+                                                            int reg_kind, float* __restrict__ ws, int64_t N, int K) {
+  __shared__ float red[3 * 4];
+  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  float part[3] = {0.f, 0.f, 0.f};  // ce, rce, reg
+  if (n < N) {
+    float v[KMAX];
+    const float* trow = soft + (size_t)n * lds;
+    const float m = load_row_max(logits + (size_t)n * ldl, K, v);
+    float ce = 0.f;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < K) ce += soft_ce_target(trow[k], ce_trunc) * logf(v[k] + 1e-6f);  // no entry skipped: 0 * NaN stays NaN
+    const float sum = exp_sum_row<KEEP_SHIFTED>(v, m, K);
+    const float lsum = logf(sum);
+    float rce = 0.f, reg = 0.f;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < K) {
+        const float lp = v[k] - lsum;
+        const float p = expf(v[k]) / sum;
+        rce += p * logf(trow[k] + 1e-6f);
+        if (reg_kind == REG_MRKLD) reg -= lp;
+        if (reg_kind == REG_MRENT) reg += p * lp;
+      }
+    part[0] = -ce;
+    part[1] = -rce;
+    part[2] = reg;
+  }
+  block_partials(part, red, ws);
+}
+
+// result = {ce, rce, reg, total, 0, 0, 0, 0}
+__global__ void soft_loss_finalize_kernel(const float* __restrict__ ws, int nblocks, int reg_kind, int64_t N, int K,
+                                          float w_ce, float w_rce, float w_reg, float* __restrict__ result) {
+  if (threadIdx.x != 0) return;
+  double s[3];
+  sum_block_partials(ws, nblocks, s);
+  const double ce = s[0] / (double)N;
+  const double rce = s[1] / (double)N;
+  const double reg = reg_kind == REG_MRKLD ? s[2] / ((double)N * K) : reg_kind == REG_MRENT ? s[2] / (double)N : 0.0;
+  // only the terms with a weight enter the total: the reference does not compute the others, and 0 * NaN would be NaN
+  double total = 0.0;
+  if (w_ce != 0.f) total += (double)w_ce * ce;
+  if (w_rce != 0.f) total += (double)w_rce * rce;
+  if (w_reg != 0.f) total += (double)w_reg * reg;
+  result[0] = (float)ce;
+  result[1] = (float)rce;
+  result[2] = (float)reg;
+  result[3] = (float)total;
+  result[4] = result[5] = result[6] = result[7] = 0.f;
+}
+
+__global__ __launch_bounds__(256) void soft_loss_bwd_kernel(const float* __restrict__ logits, int ldl,
+                                                            const float* __restrict__ soft, int lds, int ce_trunc,
+                                                            int reg_kind, const float* __restrict__ gscale, float w_ce,
+                                                            float w_rce, float w_reg, float* __restrict__ dl, int64_t N,
+                                                            int K) {
+  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const float gs = gscale ? gscale[0] : 1.f;
+  const bool use_ce = w_ce != 0.f, use_rce = w_rce != 0.f, use_reg = w_reg != 0.f && reg_kind != REG_NONE;
+  const float a_ce = gs * w_ce / (float)N;
+  const float a_rce = gs * w_rce / (float)N;
+  const float a_reg = reg_kind == REG_MRKLD ? gs * w_reg / ((float)N * (float)K) : gs * w_reg / (float)N;
+  float v[KMAX], c[KMAX], g[KMAX];
+  const float* trow = soft + (size_t)n * lds;
+  const float m = load_row_max(logits + (size_t)n * ldl, K, v);
+  // CE: autograd's log backward on the raw logit, -(a * tc) / (x + 1e-6) as written: 0/0 = NaN and -inf where the
+  // reference has them; without a weight the term is not formed at all
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k)
+    if (k < K) {
+      const float t = trow[k];
+      g[k] = use_ce ? -(a_ce * soft_ce_target(t, ce_trunc)) / (v[k] + 1e-6f) : 0.f;
+      c[k] = logf(t + 1e-6f);
+    }
+  const float sum = exp_sum_row<KEEP_SHIFTED>(v, m, K);
+  const float lsum = logf(sum);
+  // r[k] = d(a_rce*RCE + a_reg*MRENT)/dp_k of this pixel, kept in c; its softmax Jacobian is p_k (r_k - sum_j p_j r_j)
+  float pr = 0.f;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k)
+    if (k < K) {
+      const float lp = v[k] - lsum;
+      v[k] = expf(v[k]) / sum;  // p, as the forward pass has it
+      float rk = use_rce ? -a_rce * c[k] : 0.f;
+      if (use_reg && reg_kind == REG_MRENT) rk += a_reg * lp;
+      c[k] = rk;
+      pr += v[k] * rk;
+    }
+  float* out = dl + (size_t)n * ldl;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) {
+    if (k >= ldl) break;
+    float gk = 0.f;
+    if (k < K) {
+      gk = g[k] + v[k] * (c[k] - pr);
+      if (use_reg && reg_kind == REG_MRKLD) gk += a_reg * ((float)K * v[k] - 1.f);
+    }
+    out[k] = gk;
+  }
+}
+
 // ---- prototypes ---------------------------------------------------------------------------
 __global__ void proto_sigma_kernel(const float* __restrict__ proto, const float* __restrict__ sqmean,
                                    const float* __restrict__ counter, float* __restrict__ sigma, int K, int C) {
@@ -926,6 +1040,8 @@ int pixel_blocks(const float* logits, const void* out, int64_t N, int K) {
   return logits && out && K >= 1 && K <= KMAX && N >= 1 ? (int)((N + 255) / 256) : 0;
 }
 bool is_regularizer(int r) { return r >= REG_NONE && r <= REG_MRENT; }
+// these kernels read and write single floats: the siblings' rule, a pointer at a float boundary
+bool float_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 }  // namespace
 
@@ -978,6 +1094,29 @@ int onda_target_loss_bwd(const float* logits, int ldl, const int64_t* labels, in
   ONDA_REQUIRE(nb && labels && result && ldl >= K && ldl <= KMAX && is_regularizer(regularizer));
   hipLaunchKernelGGL(target_loss_bwd_kernel, dim3(nb), dim3(256), 0, ONDA_STREAM(s), logits, ldl, labels, regularizer,
                      result, gscale, w_ce, w_rce, w_reg, w_js, dlogits, N, K);
+  return ONDA_LAUNCH_RESULT();
+}
+
+int onda_soft_loss_fwd(const float* logits, int ldl, const float* soft, int lds, int ce_trunc, int regularizer, float w_ce,
+                       float w_rce, float w_reg, float* result, float* ws, int64_t N, int K, onda_stream_t s) {
+  const int nb = pixel_blocks(logits, result, N, K);
+  ONDA_REQUIRE(nb && soft && ws && ldl >= K && lds >= K && is_regularizer(regularizer));
+  if (!float_aligned(logits) || !float_aligned(soft) || !float_aligned(result) || !float_aligned(ws)) return ONDA_EALIGN;
+  hipLaunchKernelGGL(soft_loss_fwd_kernel, dim3(nb), dim3(256), 0, ONDA_STREAM(s), logits, ldl, soft, lds, ce_trunc,
+                     regularizer, ws, N, K);
+  hipLaunchKernelGGL(soft_loss_finalize_kernel, dim3(1), dim3(64), 0, ONDA_STREAM(s), ws, nb, regularizer, N, K, w_ce,
+                     w_rce, w_reg, result);
+  return ONDA_LAUNCH_RESULT();
+}
+
+int onda_soft_loss_bwd(const float* logits, int ldl, const float* soft, int lds, int ce_trunc, int regularizer, float w_ce,
+                       float w_rce, float w_reg, const float* gscale, float* dlogits, int64_t N, int K, onda_stream_t s) {
+  const int nb = pixel_blocks(logits, dlogits, N, K);
+  ONDA_REQUIRE(nb && soft && ldl >= K && ldl <= KMAX && lds >= K && is_regularizer(regularizer));
+  if (!float_aligned(logits) || !float_aligned(soft) || !float_aligned(dlogits) || (gscale && !float_aligned(gscale)))
+    return ONDA_EALIGN;
+  hipLaunchKernelGGL(soft_loss_bwd_kernel, dim3(nb), dim3(256), 0, ONDA_STREAM(s), logits, ldl, soft, lds, ce_trunc,
+                     regularizer, gscale, w_ce, w_rce, w_reg, dlogits, N, K);
   return ONDA_LAUNCH_RESULT();
 }
 

@@ -15,7 +15,8 @@ What runs where is what ``advent_da`` and ``prototypes`` say: source loss ``ops.
 the low-resolution target loss on the fused kernels ``online_proDA._target_terms`` selects.  The reference adds no EWC term in this
 step (:82-96), so none is added here.  Dropout2d masks are drawn where the passes run: source student, target student, teacher.
 
-One GPU, one stream (``advent``'s constructor raises with ``onda_amd.dist`` active); ``SOFT_LABELS`` raises as elsewhere.
+One GPU, one stream (``advent``'s constructor raises with ``onda_amd.dist`` active).  ``SOFT_LABELS`` (:24-29, :56-81) takes the
+soft-label kernels through ``_target_terms``, as in the prototype methods.
 """
 import torch
 
@@ -44,8 +45,7 @@ class adv_proDA:
         """One learning step (:23-152), in the reference's order."""
         proto, adv = self.proto_model, self.advent
         spec = proto.cfg_spec
-        if not unset(spec.SOFT_LABELS) and spec.SOFT_LABELS:
-            raise NotImplementedError("onda_amd: SOFT_LABELS is unset in the BASELINE configs; hard labels only")
+        proto._soft_labels()  # (SOFT_LABELS with JS_D > 0 raises here, before anything is launched)
         # supervised loss, on the source statistics
         adv.bn.exchange()
         adv.discriminator_grad(False)
@@ -64,7 +64,7 @@ class adv_proDA:
         proto.prototypes.ma(proto_pred["ema_model"]["feat"], proto_pred["ema_model"]["out"])
         batch_size, channels, w, h = out_trg.size()
         predictions = proto_pred["pseudolabels"].reshape(batch_size, w, h)
-        total_loss, terms = proto._target_terms(out_trg, predictions)
+        total_loss, terms = proto._target_terms(out_trg, predictions, proto_pred["soft_predictions"])
 
         # adversarial training
         ent_trg_aux, ent_trg_main = adv.entropy_map(_out(pred_trg_aux)), adv.entropy_map(out_trg)

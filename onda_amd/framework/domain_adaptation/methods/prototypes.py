@@ -425,15 +425,33 @@ class online_proDA(da_model):
         return out
 
     # ---- the target loss, pipelined ----------------------------------------------------------------------------------
-    def _target_terms(self, out, predictions):
+    def _soft_labels(self):
+        """The reference's `soft_labels` (:277-281): SOFT_LABELS, with None / {} meaning hard labels.  Soft labels with
+        JS_D > 0 fail in the reference inside js_divergance (a shape mismatch, or one_hot on a float tensor): the same
+        exception type here, raised by the step before it launches anything."""
+        soft = self.cfg_spec.SOFT_LABELS
+        soft = False if unset(soft) else soft
+        if soft and self.cfg_spec.JS_D > 0:
+            raise RuntimeError("onda_amd: SOFT_LABELS with JS_D > 0: the reference's js_divergance (loss.py:62-85) takes "
+                               "hard labels only and raises on the soft map; set JS_D to 0 or SOFT_LABELS to False")
+        return soft
+
+    def _target_terms(self, out, predictions, soft_predictions=None):
         """The low-resolution target loss on the fused kernels: (total, {log entries of its terms}) with total = CE * RCE_ALPHA
         + RCE * RCE_BETA + REGULARIZER_WEIGHT * regulariser + JS_D * JS (reference :300-333); a term whose weight is not
-        positive is logged as 0."""
+        positive is logged as 0.  With SOFT_LABELS the target is `soft_predictions`, the [N,K] soft map (reference :305-322):
+        CE over the raw logits against the truncated map (loss_calc's `.long()`: NaN in the log over negative logits, a
+        finite gradient), RCE against the real soft values -- one launch each way, whatever the regulariser."""
         spec = self.cfg_spec
         w_ce, w_rce, w_reg = _positive(spec.RCE_ALPHA), _positive(spec.RCE_BETA), _positive(spec.REGULARIZER_WEIGHT)
         w_js = _positive(spec.JS_D)
         js_loss = 0
-        if w_js > 0 or (w_reg > 0 and spec.REGULARIZER != "MRKLD"):
+        if self._soft_labels():
+            total, ce_loss, rce_loss, reg_loss = ops.soft_target_losses(out, soft_predictions, w_ce, w_rce, w_reg,
+                                                                        spec.REGULARIZER, ce_trunc=True)
+            if spec.REGULARIZER not in ops.REGULARIZERS:
+                reg_loss = 0
+        elif w_js > 0 or (w_reg > 0 and spec.REGULARIZER != "MRKLD"):
             # MRENT / an unknown regulariser (0, as the reference's regular_loss) and the JS term (reference :323-333);
             # the shipped configs (MRKLD, JS_D 0) keep the CE + RCE + MRKLD kernel below
             total, ce_loss, rce_loss, reg_loss, js_loss = ops.target_losses(out, predictions, w_ce, w_rce, w_reg,
@@ -448,7 +466,7 @@ class online_proDA(da_model):
     def _target_losses(self, out, proto_pred, cls_model):
         batch_size, channels, w, h = out.size()
         predictions = proto_pred["pseudolabels"].reshape(batch_size, w, h)
-        total, terms = self._target_terms(out, predictions)
+        total, terms = self._target_terms(out, predictions, proto_pred["soft_predictions"])
         penalty = 0
         if self.model_regularization is not None:
             # total_loss += ewc_loss(...) (reference :334-336).  The value joins the total detached: its gradient is the
@@ -495,8 +513,7 @@ class online_proDA(da_model):
     def _target_prepare(self, batch):
         """First half of the target side: Dropout2d masks (in the reference's order of draws: the student's target pass,
         then the teacher's), teacher and static forward passes.  Nothing is read back."""
-        if not unset(self.cfg_spec.SOFT_LABELS) and self.cfg_spec.SOFT_LABELS:
-            raise NotImplementedError("onda_amd: SOFT_LABELS is unset in the BASELINE configs; hard labels only")
+        self._soft_labels()  # (SOFT_LABELS with JS_D > 0 raises here, before anything is launched)
         if not unset(self.cfg_spec.PREDICTION_SAVE):
             raise NotImplementedError("onda_amd: PREDICTION_SAVE is a logging feature outside the hot path")
         image = self._device_image(batch)
@@ -768,6 +785,7 @@ class online_proDA(da_model):
         arithmetic of len(shards) ranks (x the real ranks): every micro-batch normalises with its own batch
         statistics, gradients are averaged, class statistics summed, monitor scalars averaged, the BatchNorm running
         statistics averaged, one switch decision.  Returns the first micro-batch's log dict."""
+        self._soft_labels()  # (SOFT_LABELS with JS_D > 0 raises here, before anything is launched)
         n = len(shards)
         scale = 1.0 / n
         deferred, src_log, prepared = _Scalars(), {}, []

@@ -1,4 +1,5 @@
-"""The segmentation head's tail: class slices, fused CE / RCE / MRKLD (and, off the default path, MRENT and the JS term),
+"""The segmentation head's tail: class slices, fused CE / RCE / MRKLD (and, off the default path, MRENT and the JS term, and
+the same loss against a soft target),
 softmax statistics, bilinear upsampling (+ fused cross-entropy / argmax / confusion matrix / calibration table / ADVENT's
 entropy map), the device-side prior select."""
 import ctypes
@@ -126,6 +127,63 @@ def target_losses(out, labels, w_ce=1.0, w_rce=0.0, w_reg=0.0, regularizer="MRKL
     """The reference's whole hard-label target loss (prototypes.py:299-333): (total, ce, rce, reg, js)."""
     return TargetLossFn.apply(out, labels, float(w_ce), float(w_rce), float(w_reg), REGULARIZERS.get(regularizer, 0),
                               float(w_js))
+
+
+def soft_rows_of(soft, N, K, device):
+    """(tensor, ld) of a soft target as pixel-major float32 rows: the [N,K] map itself (no copy), or an NCHW tensor, float
+    or integer, brought to rows (no copy either where it is a view of such a map)."""
+    if soft.dim() == 4:
+        soft = soft.permute(0, 2, 3, 1).reshape(-1, soft.shape[1])
+    if soft.dim() != 2 or tuple(soft.shape) != (N, K):
+        raise ValueError(f"soft_target_losses: a soft target of shape {tuple(soft.shape)} for {N} pixels of {K} classes")
+    soft = soft.detach().to(device=device, dtype=torch.float32)
+    if soft.stride(1) != 1 or soft.stride(0) < K:
+        soft = soft.contiguous()
+    return soft, soft.stride(0)
+
+
+class SoftLossFn(torch.autograd.Function):
+    """w_ce*CE + w_rce*RCE + w_reg*reg against a SOFT target (the reference's SOFT_LABELS branch), one pass each way; reg
+    as in TargetLossFn.  CE reads the raw logits -- NaN over negative ones, with a finite gradient -- against trunc(target)
+    (ce_trunc, func.loss_calc's `.long()`) or the target itself; RCE uses the real soft values (include/onda_hip.h).
+    Returns (total, ce, rce, reg) with gradients flowing through `total` only; a term whose weight is 0 is left out of
+    `total` and of the gradient."""
+
+    @staticmethod
+    def forward(ctx, out, soft, w_ce, w_rce, w_reg, regularizer, ce_trunc):
+        rows, ld, N, K = logits_rows(out)
+        soft, lds = soft_rows_of(soft, N, K, out.device)
+        result = torch.empty(8, device=out.device, dtype=torch.float32)
+        ws = torch.empty(8 * (N // 256 + 1), device=out.device, dtype=torch.float32)
+        call("onda_soft_loss_fwd", _p(rows), ld, _p(soft), lds, ce_trunc, regularizer, w_ce, w_rce, w_reg, _p(result), _p(ws),
+             N, K, _stream())
+        ctx.save_for_backward(rows, soft)
+        ctx.shape = tuple(out.shape)
+        ctx.set_materialize_grads(False)
+        ctx.meta = (ld, lds, N, K, w_ce, w_rce, w_reg, regularizer, ce_trunc)
+        ce, rce, reg, total = result[0], result[1], result[2], result[3].clone()
+        ctx.mark_non_differentiable(ce, rce, reg)
+        return total, ce, rce, reg
+
+    @staticmethod
+    def backward(ctx, gtotal, _a, _b, _c):
+        if gtotal is None:
+            return None, None, None, None, None, None, None
+        rows, soft = ctx.saved_tensors
+        ld, lds, N, K, w_ce, w_rce, w_reg, regularizer, ce_trunc = ctx.meta
+        B, _, H, W = ctx.shape
+        g = gtotal.reshape(1).to(torch.float32).contiguous()
+        dl = torch.empty(B, H, W, ld, device=rows.device, dtype=torch.float32)
+        call("onda_soft_loss_bwd", _p(rows), ld, _p(soft), lds, ce_trunc, regularizer, w_ce, w_rce, w_reg, _p(g), _p(dl), N, K,
+             _stream())
+        return dl[..., :K].permute(0, 3, 1, 2), None, None, None, None, None, None
+
+
+def soft_target_losses(out, soft_rows, w_ce=1.0, w_rce=0.0, w_reg=0.0, regularizer="MRKLD", ce_trunc=True):
+    """The reference's soft-label target loss (prototypes.py:305-328 with SOFT_LABELS): (total, ce, rce, reg).  `soft_rows`:
+    the [N,K] soft map in the pixel order of `out`, or an NCHW tensor (float or int64)."""
+    return SoftLossFn.apply(out, soft_rows, float(w_ce), float(w_rce), float(w_reg), REGULARIZERS.get(regularizer, 0),
+                            int(bool(ce_trunc)))
 
 
 def softmax_stats(out, want_probs=False, want_argmax=False):
