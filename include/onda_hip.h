@@ -502,6 +502,20 @@ int onda_ece_bins_local(void);
 int onda_upsample_ece(const float* rows, int ld, const uint8_t* labels, int64_t* table, int bins, int probs, int64_t* hist, int B,
                       int h, int w, int K, int H, int W, onda_stream_t s);
 
+/* ---- evaluate_model's per-batch tail (eval_UDA.py:47-57, func.py:71-79) in one read of the low-resolution rows ----
+ * rows: [B*h*w] rows of ldl floats, 2 <= K <= 32 classes in front (the divisor is log2(K); the K values of a pixel stay in
+ * registers).  Every output pixel of the align_corners bilinear upsample to HxW is reduced to its class (first maximum, as
+ * onda_upsample_argmax) and to e = sum_k -p_k * log2(p_k + 1e-30) / log2(K), p = softmax over its K interpolated values, the
+ * per-element float32 expression of onda_upsample_entropy_fwd summed over k in index order:
+ *   ent[0] += round(e * 2^32)  for a finite e        ent[1] += 1  otherwise (NaN or +inf among the pixel's values)
+ * for every pixel, whatever its label: prob_2_entropy(softmax(interp(x), 1)).mean() = ent[0] / 2^32 / (B*K*H*W), NaN when
+ * ent[1] > 0.  B*H*W <= 2^31.  Integer adds, one per workgroup and counter: the sums do not depend on the order or the grid.
+ * labels u8[B,H,W] with hist int64[K*K]: the confusion matrix exactly as onda_upsample_argmax_hist counts it (labels >= K
+ * ignored), in the same pass; both null: no matrix.  cls (optional) u8[B,H,W] receives the class map.  ent int64[2] and hist are
+ * accumulated (zero them first). */
+int onda_upsample_eval(const float* rows, int ldl, const uint8_t* labels, int64_t* hist, int64_t* ent, uint8_t* cls, int B, int h,
+                       int w, int K, int H, int W, onda_stream_t s);
+
 /* ---- per-pixel softmax statistics --------------------------------------------------------
  * probs (optional, rows of stride ldp) = softmax(logits row); argmax (optional int32);
  * result[0] = mean over pixels of the max probability (the "prior ..." / "model" monitor

@@ -150,6 +150,7 @@ SIGNATURES = {
     "onda_upsample_argmax_hist": (I, [P, I, P, P, P, I, I, I, I, I, I, P]),
     "onda_ece_bins_local": (I, []),
     "onda_upsample_ece": (I, [P, I, P, P, I, I, P, I, I, I, I, I, I, P]),
+    "onda_upsample_eval": (I, [P, I, P, P, P, P, I, I, I, I, I, I, P]),
     "onda_softmax_stats": (I, [P, I, P, I, P, P, P, L, I, P]),
     "onda_seg_loss_fwd": (I, [P, I, P, P, P, L, I, P]),
     "onda_seg_loss_bwd": (I, [P, I, P, P, P, F, F, F, P, L, I, P]),

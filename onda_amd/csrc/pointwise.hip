@@ -1,5 +1,6 @@
 // HBM-bound pointwise / stencil kernels of the hot path: ceil-mode max-pool, the SE gate,
-// channel scaling, align_corners bilinear upsampling (plain, gradient, fused argmax / cross-entropy / calibration / entropy map).
+// channel scaling, align_corners bilinear upsampling (plain, gradient, fused argmax / cross-entropy / calibration / entropy map /
+// validation tail).
 #include "limbs.h"
 #include <type_traits>
 
@@ -649,6 +650,74 @@ __global__ __launch_bounds__(256) void upsample_entropy_kernel(const float* __re
   }
 }
 
+// ---- evaluate_model's per-batch tail (eval_UDA.py:47-57): upsample -> argmax -> confusion matrix, and the batch's entropy ------
+// prob_2_entropy(softmax(interp(x), 1)).mean() needs the sum of the entropy map, not the map: one thread per output pixel keeps
+// its K interpolated logits in registers, takes the class (the first-maximum rule and the counting of upsample_kernel<true>:
+// the same expression, so the same class map and the same matrix), then the softmax and e = sum_k I_k in index order, and adds
+//   ent[0] += round(e * 2^32) for a finite e (0 <= e <= ~1: 2^31 pixels fit an int64), ent[1] += 1 otherwise (a NaN or +inf
+// among the pixel's logits).  Every pixel counts, whatever its label.  The sums are taken per thread, then per wave, then per
+// workgroup through LDS: one global atomic per workgroup and non-zero counter.  Integer adds: any grid, any order, one result.
+__device__ __forceinline__ long long wave_sum_ll(long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void upsample_eval_kernel(const float* __restrict__ rows, int ldl, const uint8_t* __restrict__ gt,
+                                                            unsigned long long* __restrict__ hist,
+                                                            unsigned long long* __restrict__ ent, uint8_t* __restrict__ cls, int B,
+                                                            int h, int w, int K, int H, int W, float sy, float sx, float log2k) {
+  __shared__ unsigned lh[UPS_HIST_LDS];  // K <= UCE_KMAX: K * K cells always fit
+  __shared__ long long red_sum[4];
+  __shared__ long long red_bad[4];
+  const int KK = K * K;
+  if (hist) {
+    lds_zero(lh, KK);
+    __syncthreads();
+  }
+  const bool vec = ROWS_VEC(rows, ldl, K);
+  const size_t total = (size_t)B * H * W;
+  long long sum = 0, bad = 0;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    const Pixel p = pixel_at(e, rows, ldl, h, w, H, W, sy, sx);
+    float v[UCE_KMAX];
+    if (vec) {
+#pragma unroll
+      for (int k = 0; k < UCE_KMAX; k += 4)
+        if (k < K) bilerp4(p, true, k, K, &v[k]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < UCE_KMAX; ++k)
+        if (k < K) v[k] = bilerp(p.ly, p.lx, p.p00[k], p.p01[k], p.p10[k], p.p11[k]);
+    }
+    float best = -INFINITY;
+    int arg = 0;
+#pragma unroll
+    for (int k = 0; k < UCE_KMAX; ++k)
+      if (k < K && v[k] > best) best = v[k], arg = k;
+    if (cls) cls[e] = (uint8_t)arg;
+    if (hist) hist_count(lh, hist, true, gt[e], arg, K);
+    ent_softmax(v, K);
+    float en = 0.f;
+#pragma unroll
+    for (int k = 0; k < UCE_KMAX; ++k)
+      if (k < K) en += -(v[k] * log2f(v[k] + ENT_EPS)) / log2k;
+    if (fabsf(en) <= 3.402823466e38f) sum += __float2ll_rn(en * ECE_FIX);
+    else bad += 1;
+  }
+  sum = wave_sum_ll(sum);
+  bad = wave_sum_ll(bad);
+  if ((threadIdx.x & 63) == 0) red_sum[threadIdx.x >> 6] = sum, red_bad[threadIdx.x >> 6] = bad;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    sum = red_sum[0] + red_sum[1] + red_sum[2] + red_sum[3];
+    bad = red_bad[0] + red_bad[1] + red_bad[2] + red_bad[3];
+    if (sum) atomicAdd(&ent[0], (unsigned long long)sum);
+    if (bad) atomicAdd(&ent[1], (unsigned long long)bad);
+  }
+  if (hist) flush_rotated(lh, hist, KK);  // (behind the barrier above)
+}
+
 // ---- the two-pass backward of the fused heads -----------------------------------------------------------------------------
 // Gradient with respect to the LOW-resolution logits.  The interpolation weights are separable, so
 //     dl[y][x][k] = sum_Y wy(Y, y) * ( sum_X wx(X, x) * g[Y][X][k] ),   g = the head's gradient with respect to a pixel's
@@ -969,6 +1038,20 @@ int onda_upsample_ece(const float* rows, int ld, const uint8_t* labels, int64_t*
   else
     hipLaunchKernelGGL((upsample_ece_kernel<false>), dim3(grid), dim3(256), lds, ONDA_STREAM(s), rows, ld, labels, t, bins, gap,
                        probs ? 1 : 0, hh, B, h, w, K, H, W, sy, sx, local);
+  return ONDA_LAUNCH_RESULT();
+}
+
+int onda_upsample_eval(const float* rows, int ldl, const uint8_t* labels, int64_t* hist, int64_t* ent, uint8_t* cls, int B, int h,
+                       int w, int K, int H, int W, onda_stream_t s) {
+  ONDA_REQUIRE(rows && ent && (labels != nullptr) == (hist != nullptr) && K >= 2 && K <= UCE_KMAX && K <= ldl && B >= 1 && h >= 1 &&
+               w >= 1 && H >= 1 && W >= 1);
+  const size_t total = (size_t)B * H * W;
+  ONDA_REQUIRE(total <= (1ull << 31));  // ent[0] in 2^-32 steps, e <= ~1; a workgroup's LDS counts are 32 bits wide
+  unsigned grid = ew_grid(total);
+  if (grid > 1024u) grid = 1024u;  // one flush of the workgroup's counts each (onda_upsample_argmax_hist)
+  hipLaunchKernelGGL(upsample_eval_kernel, dim3(grid), dim3(256), 0, ONDA_STREAM(s), rows, ldl, labels,
+                     reinterpret_cast<unsigned long long*>(hist), reinterpret_cast<unsigned long long*>(ent), cls, B, h, w, K, H, W,
+                     ac_scale(h, H), ac_scale(w, W), (float)log2((double)K));
   return ONDA_LAUNCH_RESULT();
 }
 

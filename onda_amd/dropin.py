@@ -7,7 +7,7 @@ _MODULES = [
     "framework", "framework.model", "framework.model.deeplabv2", "framework.model.deeplabv2_proda", "framework.model.discriminator", "framework.handlers",
     "framework.handlers.model_handler", "framework.handlers.adaptation_method_handler",
     "framework.utils", "framework.utils.func", "framework.utils.loss", "framework.utils.monitoring",
-    "framework.domain_adaptation", "framework.domain_adaptation.methods",
+    "framework.domain_adaptation", "framework.domain_adaptation.eval_UDA", "framework.domain_adaptation.methods",
     "framework.domain_adaptation.methods.adaptation_model", "framework.domain_adaptation.methods.prototype_handler",
     "framework.domain_adaptation.methods.prototypes", "framework.domain_adaptation.methods.prototypes_hybrid_switch",
     "framework.domain_adaptation.methods.prototypes_hswitch", "framework.domain_adaptation.methods.prototypes_vswitch",

@@ -9,12 +9,13 @@ WHERE the per-sample arithmetic runs:
   * `gpu_collate(samples)` (the training process) uploads them and runs
     `onda_amd.pipeline.GpuPreprocessor` -- Pillow's BICUBIC resize, BGR flip, ToTensor + Normalize,
     the two NEAREST label resizes and the id map, bit-identical to the reference's CPU path --
-    returning the reference's batch dict: `image`, `label`, `label_res`, `image_path`, `label_path`.
+    returning the reference's batch dict: `image`, `label`, `label_res`, `image_path`, `label_path`, and with
+    `original_label=True` also `label_raw` u8[B,H0,W0] -- the id map on the un-resized label (:71,76-77), what
+    `evaluate_model(..., intrp_org=...)` reads; the frames of a batch then need one native size.
 
 Use: `DataLoader(ds, batch_size=4, num_workers=7, collate_fn=lambda s: s)` and call
 `ds.gpu_collate(samples)` on what it yields (a GPU context must not be created inside workers).
-Not mirrored (out of scope): RGB-coded label maps, `soft_predictions` caching,
-`original_label`.
+Not mirrored (out of scope): RGB-coded label maps, `soft_predictions` caching.
 """
 from os import path
 
@@ -27,7 +28,7 @@ from ...pipeline import GpuPreprocessor
 
 class Segmentation_db(torch.utils.data.Dataset):
     def __init__(self, root_folder, pandas_metadata, class_map, image_size, labels_size=None, mean=(0.0, 0.0, 0.0),
-                 std=(255.0, 255.0, 255.0), device="cuda:0"):
+                 std=(255.0, 255.0, 255.0), device="cuda:0", original_label=False):
         """mean / std in [0, 255] (what the reference passes to `base_transform(mean, std)`,
         train_ouda.py:100-111); class_map: dict source id -> train id (`color_mapper`, rgb False)."""
         self.metadata = pandas_metadata
@@ -43,6 +44,7 @@ class Segmentation_db(torch.utils.data.Dataset):
         else:
             lut = np.asarray(class_map)
         self._args = (tuple(self.image_size), tuple(self.labels_size), tuple(mean), tuple(std), lut, device)
+        self.original_label = bool(original_label)
         self._pre = None  # built lazily in the process that owns the GPU
 
     def __len__(self):
@@ -64,7 +66,10 @@ class Segmentation_db(torch.utils.data.Dataset):
             size, lsize, mean, std, lut, device = self._args
             self._pre = GpuPreprocessor(size, lsize, mean, std, lut, device)
         labs = [s["label_ids"] for s in samples] if all("label_ids" in s for s in samples) else None
-        batch = self._pre.batch([s["image_raw"] for s in samples], labs)
+        if self.original_label and labs is not None:
+            batch = self._pre.batch([s["image_raw"] for s in samples], labs, original_label=True)
+        else:
+            batch = self._pre.batch([s["image_raw"] for s in samples], labs)
         batch["image_path"] = [s["image_path"] for s in samples]
         if labs is not None:
             batch["label_path"] = [s["label_path"] for s in samples]

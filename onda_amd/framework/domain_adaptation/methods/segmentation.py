@@ -5,9 +5,11 @@ cross-entropy -> backward -> SGD with the duplicated parameter groups -> poly le
 ``train(model, train_loader, validation_loaders, cfg, cfg_spec)`` keeps the reference's signature and loop
 (:62-100); the unit of work lives in ``SegmentationTrainer.step`` so that bench.py can time exactly it.  Every
 forward/backward op is a HIP kernel; the loss is evaluated on the upsampled logits by the fused loss kernel;
-validation uses the fused upsample -> argmax -> confusion-matrix kernel (adaptation_model.da_model.evaluate).
-Not mirrored (outside SURVEY section 8): the DOMAIN_ANALYSIS branch, sample images, entropy logging, the
-per-phase timers (PytorchSpeedMeasure).
+validation is ``eval_UDA.evaluate_model`` (:102-121) on the fused upsample -> argmax -> confusion-matrix -> entropy kernel:
+mIoU, its standard deviation over the classes, the mean entropy of the prediction and, with SCHEME.ORIGINAL_RES, mIoU
+against the labels at their native size (the loader then has to supply ``label_raw``: ``Segmentation_db(original_label=True)``).
+Not mirrored (outside SURVEY section 8): the DOMAIN_ANALYSIS branch, sample images, the per-phase timers
+(PytorchSpeedMeasure).
 """
 import os
 
@@ -18,6 +20,7 @@ from onda_amd import dist as odist
 from onda_amd import logging as olog
 from onda_amd import ops
 from onda_amd.config import unset
+from onda_amd.framework.domain_adaptation.eval_UDA import evaluate_model
 from onda_amd.framework.model.deeplabv2 import require_single_gpu_affine, unused_head_skip
 from onda_amd.framework.utils.func import lr_poly, per_class_iu
 from onda_amd.optim import ReplaySGD
@@ -108,6 +111,19 @@ class SegmentationTrainer:
         self.model.train()
         return per_class_iu(hist.cpu().numpy())
 
+    @property
+    def original_size(self):
+        """(H, W) of SCHEME.ORIGINAL_RES when it is set and differs from RESOLUTION (reference :49-54), else None."""
+        res = self.cfg.SCHEME.ORIGINAL_RES
+        if unset(res) or list(res) == list(self.cfg.SCHEME.RESOLUTION):
+            return None
+        return tuple(res[::-1])
+
+    def validate(self, loader):
+        """evaluate_model as the reference's train() calls it (:105-118): (IoU, entropy), or (IoU, entropy, IoU at the
+        labels' native size) with SCHEME.ORIGINAL_RES."""
+        return evaluate_model(self.model, loader, self.size, self.cfg, return_entropy=True, intrp_org=self.original_size)
+
 
 def save_model(model, epoch, cfg):
     """``model_train_<source set>.pth`` under the snapshot directory, overwritten every epoch (reference :141-151: the file
@@ -137,9 +153,12 @@ def train(model, train_loader, validation_loaders, cfg, cfg_spec=None):
                 pending = []
         log = {"epoch": epoch}
         for name, val_loader in (validation_loaders or {}).items():
-            iou = trainer.evaluate(val_loader)
+            iou, entropy, *full = trainer.validate(val_loader)
+            if full:
+                log[f"Val mIoU full image of {name}"] = np.nanmean(full[0])
             log[f"Val mIoU of {name}"] = np.nanmean(iou)
             log[f"Val std IoU of {name}"] = np.nanstd(iou)
+            log[f"val entropy of {name}"] = entropy
         olog.log(log)
         save_model(model, epoch, cfg)
     return trainer

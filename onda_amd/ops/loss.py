@@ -366,6 +366,102 @@ def upsample_ece(out_or_rows, labels, table, bins, probs=False, hist=None, num_c
     return table
 
 
+EVAL_FIX = 4294967296.0  # 2^32: the fixed point of ent[0] (ECE_FIX of csrc/pointwise.hip)
+EVAL_KMIN, EVAL_KMAX = 2, 32  # classes onda_upsample_eval takes (the K-vector of a pixel stays in registers)
+EVAL_FUSED = True  # False (the tests): upsample_eval takes the composed route on the GPU as well
+
+
+def _eval_args(out_or_rows, labels, hist, num_classes, cls, shape):
+    """What upsample_eval and upsample_eval_composed share: the checks of upsample_ece -> (NCHW view, labels u8 or None, (H, W))."""
+    if out_or_rows.dim() == 2:
+        if shape is None:
+            raise ValueError("upsample_eval: an [N,K] map needs shape=(B, h, w)")
+        B, h, w = shape
+        N, K = out_or_rows.shape
+        if N != B * h * w:
+            raise ValueError(f"upsample_eval: {N} rows for shape {tuple(shape)}")
+        out_or_rows = out_or_rows.reshape(B, h, w, K).permute(0, 3, 1, 2)
+    if out_or_rows.dtype != torch.float32:
+        raise TypeError("upsample_eval: float32 only")
+    B, K = out_or_rows.shape[:2]
+    dev = out_or_rows.device
+    if num_classes is not None and num_classes != K:
+        raise ValueError(f"upsample_eval: {K} classes in the map, num_classes = {num_classes}")
+    if (labels is None) != (hist is None):
+        raise ValueError("upsample_eval: labels and hist are given together or not at all")
+    if labels is not None:
+        labels = labels.to(device=dev, dtype=torch.uint8).contiguous()
+        if labels.dim() != 3 or labels.shape[0] != B:
+            raise ValueError(f"upsample_eval: labels of shape {tuple(labels.shape)} for a batch of {B}")
+        size = tuple(labels.shape[1:])
+        if hist.dtype != torch.int64 or hist.numel() != K * K or not hist.is_contiguous() or hist.device != dev:
+            raise ValueError(f"upsample_eval: hist must be contiguous int64 [{K}, {K}] on {dev}")
+    elif cls is None:
+        raise ValueError("upsample_eval: without labels the size comes from cls u8[B,H,W]")
+    else:
+        size = tuple(cls.shape[1:])
+    if cls is not None and (cls.dtype != torch.uint8 or tuple(cls.shape) != (B,) + size or not cls.is_contiguous() or cls.device != dev):
+        raise ValueError(f"upsample_eval: cls must be contiguous uint8 {(B,) + size} on {dev}")
+    return out_or_rows, labels, size
+
+
+def upsample_eval_composed(out_or_rows, labels, hist, num_classes, cls=None, shape=None):
+    """evaluate_model's per-batch tail the way the reference composes it (eval_UDA.py:47-57): interp (UpsampleFn on the GPU,
+    F.interpolate elsewhere) -> torch softmax -> the entropy expression -> .mean(), three [B,K,H,W] tensors in memory, and the
+    confusion matrix of the upsampled argmax (ops.upsample_argmax_hist on the GPU, fast_hist's bincount elsewhere) accumulated
+    into `hist`.  Returns the batch's entropy mean, a float32 scalar on the input's device.  Arguments as upsample_eval; any K.
+    The yardstick of tools/eval_timing.py and of the tests."""
+    out, labels, size = _eval_args(out_or_rows, labels, hist, num_classes, cls, shape)
+    K = out.shape[1]
+    with torch.no_grad():
+        if out.is_cuda:
+            up = UpsampleFn.apply(out, size)
+        else:
+            up = torch.nn.functional.interpolate(out, size=size, mode="bilinear", align_corners=True)
+        p = torch.softmax(up, 1)
+        mean = (-torch.mul(p, torch.log2(p + 1e-30)) / math.log2(K)).mean()
+        if labels is not None:
+            if out.is_cuda and K <= 255:
+                upsample_argmax_hist(out, labels, hist, K)
+            else:
+                a, b = labels.reshape(-1).long(), up.argmax(1).reshape(-1)
+                keep = a < K  # fast_hist (func.py:77-79): rows = ground truth in [0, K), columns = prediction
+                hist.view(-1).add_(torch.bincount(K * a[keep] + b[keep], minlength=K * K))
+        if cls is not None:
+            cls.copy_(upsample_argmax(out, size) if out.is_cuda and K <= 255 else up.argmax(1))
+    return mean
+
+
+def upsample_eval(out_or_rows, labels, hist, num_classes, ent, cls=None, shape=None):
+    """evaluate_model's per-batch tail (eval_UDA.py:47-57) in one launch and one read of the low-resolution map, without the
+    upsampled tensor: hist i64[K,K] (accumulated) += the confusion matrix of upsample_argmax_hist, `cls` (optional u8[B,H,W])
+    = the class map, and ent i64[2] (accumulated) += (sum over the pixels of round(e * 2^32), pixels with a non-finite e),
+    e = the sum over the classes of prob_2_entropy(softmax(interp(out), 1)) (include/onda_hip.h); entropy_mean turns `ent`
+    into the reference's `.mean()`.  `out_or_rows`: NCHW logits, or an [N,K] map with shape=(B, h, w); labels u8[B,H,W] give
+    the size (labels = hist = None: `cls` does).  Off the GPU, or with K outside [2, 32], upsample_eval_composed does the
+    work and its mean is written into `ent` in the same fixed point."""
+    out, labels, size = _eval_args(out_or_rows, labels, hist, num_classes, cls, shape)
+    if ent.dtype != torch.int64 or tuple(ent.shape) != (2,) or not ent.is_contiguous() or ent.device != out.device:
+        raise ValueError(f"upsample_eval: ent must be contiguous int64 [2] on {out.device}")
+    B, K, h, w = out.shape
+    if not out.is_cuda or not EVAL_KMIN <= K <= EVAL_KMAX or not EVAL_FUSED:
+        mean = upsample_eval_composed(out, labels, hist, num_classes, cls=cls).double()
+        ok = torch.isfinite(mean)
+        total = torch.round(torch.where(ok, mean, torch.zeros_like(mean)) * (float(B * K * size[0] * size[1]) * EVAL_FIX))
+        ent.add_(torch.stack([total.long(), (~ok).long()]))
+        return ent
+    rows, ld, _, _ = logits_rows(out)
+    call("onda_upsample_eval", _p(rows), ld, _p(labels), _p(hist), _p(ent), _p(cls), B, h, w, K, size[0], size[1], _stream())
+    return ent
+
+
+def entropy_mean(ent, B, K, H, W):
+    """prob_2_entropy(F.softmax(interp(x), 1)).mean() of a batch from upsample_eval's `ent`: ent[0] / 2^32 / (B*K*H*W) as a
+    float64 scalar on ent's device; NaN when a pixel's entropy was not finite (ent[1] > 0)."""
+    mean = ent[0].double() / EVAL_FIX / float(B * K * H * W)
+    return torch.where(ent[1] > 0, torch.full_like(mean, float("nan")), mean)
+
+
 # ------------------------------------------------------------------------------- device-side switch
 def select_prior(flag, a, wa, b, wb):
     """flag ? wb * b : wa * a, elementwise, as a true select (`b` may be garbage when flag == 0).  `a` and `b` may be any

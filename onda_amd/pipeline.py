@@ -127,12 +127,27 @@ class GpuPreprocessor:
         W, H = self.labels_size
         return self._label(lab_u8, (W, H)), self._label(lab_u8, (int(W / 8 + 1), int(H / 8 + 1)))
 
-    def batch(self, frames, label_frames=None):
+    def label_raw(self, lab_u8):
+        """u8[H0, W0] id image on the device -> `label_raw` u8[H0, W0]: the id map on the un-resized label (reference
+        segmentation_db.py:71,76-77), the nearest-resize kernel under identity index tables."""
+        if lab_u8.dtype != torch.uint8 or lab_u8.dim() != 2 or not lab_u8.is_cuda:
+            raise RuntimeError("onda_amd.pipeline: label must be a uint8 [H, W] tensor on the GPU")
+        H0, W0 = lab_u8.shape
+        return self._label(lab_u8.contiguous(), (W0, H0))
+
+    def batch(self, frames, label_frames=None, original_label=False):
         """Lists of decoded frames -> the batch dict fields the adaptation step reads
-        (`image` f32[B,3,H,W], `label` u8[B,H,W], `label_res` u8[B,H/8+1,W/8+1])."""
+        (`image` f32[B,3,H,W], `label` u8[B,H,W], `label_res` u8[B,H/8+1,W/8+1]); with `original_label` also `label_raw`
+        u8[B,H0,W0], which needs frames of one size (the reference's default_collate cannot stack others either)."""
         out = {"image": torch.stack([self.image(f.to(self.device, non_blocking=True)) for f in frames])}
         if label_frames is not None:
-            pairs = [self.labels(f.to(self.device, non_blocking=True)) for f in label_frames]
+            on_device = [f.to(self.device, non_blocking=True) for f in label_frames]
+            pairs = [self.labels(f) for f in on_device]
             out["label"] = torch.stack([p[0] for p in pairs])
             out["label_res"] = torch.stack([p[1] for p in pairs])
+            if original_label:
+                sizes = sorted({tuple(f.shape) for f in on_device})
+                if len(sizes) != 1:
+                    raise RuntimeError(f"onda_amd.pipeline: label_raw needs labels of one native size in a batch, got {sizes}")
+                out["label_raw"] = torch.stack([self.label_raw(f) for f in on_device])
         return out
